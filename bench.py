@@ -1,14 +1,15 @@
 #!/usr/bin/env python3
 """bench.py -- frames/s of the per-frame pipe on synthetic 1080p frames.
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
 
 A "step" is one pass of the hot path (bgdehaze -> histretch -> aclahe ->
 videostrip-overlap) over one batch of synthetic 1920x1080 uchar3 frames that is
 already resident in HBM.  Frames are independent units: with N > 1 every rank
 runs the same per-GPU batch on its own GPU (weak scaling, no data-path
 collective; torch.distributed is used only for the barrier and the max-over-
-ranks time).  Rank 0 prints ONE JSON line with the whole-job frames/s, the HBM
+ranks time).  Rank 0 prints ONE JSON line with the whole-job frames/s.  A plain
+run does only that; with --full the line also carries the self-checks, the HBM
 roofline of the dominant kernel (timed live with HIP events on the launch
 stream) and the CPU baseline (the oracle, timed on a bounded sample).
 """
@@ -55,6 +56,11 @@ def parse():
                     help="frames gathered before the pipe runs (latency vs launch size; measured at 4K@60: batch 1 -> 7 ms worst "
                          "arrival-to-delivery latency, 2 -> 29 ms, 4 -> 67 ms, all three keep up)")
     ap.add_argument("--streams", type=int, default=8, help="independent sub-batches in flight per GPU (HIP streams + host threads)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one handed its caller as DIR/<name>.npy (see dump_outputs)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also run the self-checks, the host-buffer leg, the per-kernel / roofline pass, the "
+                         "further scenes, the 4K leg and the CPU baseline; the --no-* / --scenes options below apply to these")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-matcher-bench", dest="matcher_bench", action="store_false",
                     help="skip the 2048 x 2048 matcher measurement (MFMA utilisation on BASELINE config 4's size)")
@@ -251,6 +257,34 @@ def outputs_identical(rig):
     for p in rig.pipes[1:]:
         ok = ok and bool(torch.equal(p.work, p0.work)) and bool(torch.equal(p.ratio, p0.ratio)) and list(p.params) == list(p0.params)
     return ok
+
+
+DUMP_FRAME_BYTES = 48 << 20      # the enhanced frames' share of --dump-outputs (everything together stays under 64 MB)
+
+
+def dump_outputs(rig, path):
+    """What the last timed step handed its caller (FramePipe.run -> uwip_pipe_step, then uwip_pipe_last_params), frames in
+    sub-batch order, so that two builds can be compared output for output on the same seeded inputs (call after rig.drain()):
+      enhanced.npy               float32 [F, H, W, 3] -- or, when that exceeds DUMP_FRAME_BYTES, [F, P, 3]: every frame at
+                                 the same P pixel positions, a fixed seeded sample listed in enhanced_pixel_index.npy
+      enhanced_pixel_index.npy   float64 [P] row-major pixel indices (y * W + x), only when sampled
+      overlap_ratio.npy          float32 [F]
+      aclahe_params.npy          float64 [F, 2] (BS, CL) of every frame"""
+    os.makedirs(path, exist_ok=True)
+    F, H, W = rig.F, rig.H, rig.W
+    out = {"overlap_ratio": torch.cat([p.ratio for p in rig.pipes]).float().cpu().numpy(),
+           "aclahe_params": np.array([bc for p in rig.pipes for bc in p.params], dtype=np.float64)}
+    if F * H * W * 3 * 4 <= DUMP_FRAME_BYTES:
+        out["enhanced"] = torch.cat([p.work for p in rig.pipes]).float().cpu().numpy()
+    else:
+        P = max(1, min(H * W, DUMP_FRAME_BYTES // (F * 3 * 4)))
+        pix = np.sort(np.random.default_rng(20240611).choice(H * W, P, replace=False))
+        idx = torch.from_numpy(pix).to(rig.dev)
+        out["enhanced"] = torch.cat([p.work.view(rig.Fs, H * W, 3).index_select(1, idx) for p in rig.pipes]).float().cpu().numpy()
+        out["enhanced_pixel_index"] = pix.astype(np.float64)
+    assert sum(a.nbytes for a in out.values()) <= 64 << 20
+    for name, a in out.items():
+        np.save(os.path.join(path, name + ".npy"), a)
 
 
 def spot_capture(rig, dev_index):
@@ -924,11 +958,14 @@ def main():
 
     dt = timed(rig, world, args.steps, args.warmup, host=False)
     host_cpu_s = sharding.max_over_ranks(rig.last_host_cpu_s)
-    # what was timed is also checked: the S sub-batches hold the same frames, so every pipe must hold the same result
-    same_out = sharding.max_over_ranks(0.0 if outputs_identical(rig) else 1.0) == 0.0
-    spot = spot_capture(rig, dev_index) if (rank == 0 and not args.no_cpu_baseline) else None
+    if args.dump_outputs and rank == 0:
+        dump_outputs(rig, args.dump_outputs)
+    # everything below the headline is --full's.  What was timed is also checked: the S sub-batches hold the same frames,
+    # so every pipe must hold the same result
+    same_out = (sharding.max_over_ranks(0.0 if outputs_identical(rig) else 1.0) == 0.0) if args.full else None
+    spot = spot_capture(rig, dev_index) if (args.full and rank == 0 and not args.no_cpu_baseline) else None
 
-    host = host_leg(rig, world, args.steps) if args.host_buffers else None
+    host = host_leg(rig, world, args.steps) if (args.full and args.host_buffers) else None
     if host is not None:
         host["host_cpu_s_per_step"] = sharding.max_over_ranks(rig.last_host_cpu_s) / args.steps
 
@@ -936,12 +973,12 @@ def main():
     roof = None
     kernels = {}
     stages = pipe.stages()
-    if rank == 0:
+    if args.full and rank == 0:
         roof, kernels = roofline_report(args, pipe, rig.parts[0], dev, F, rig.Fs, H, W)
     barrier(world)
     # the same timed region on further scenes (every rank; rank r's scenes differ from rank 0's as its headline scene does)
     scenes = None
-    if args.scenes > 1:
+    if args.full and args.scenes > 1:
         sc_steps = max(1, min(args.steps, 5))
         scenes = [{"seed0": rig.seed0, "frames_per_s": world * F * args.steps / dt, "ms_per_step": dt / args.steps * 1e3, "steps": args.steps,
                    "sweep_ms_per_subbatch": (kernels.get("k_clahe_sweep") or {}).get("ms_per_subbatch"), "is": "the headline scene (`value`)"}]
@@ -960,7 +997,7 @@ def main():
     if args.config == "4k-paced":
         paced = paced_stream(args, dev_index, dev, H, W)
     fourk = None
-    if args.config == "1080p" and args.fourk and (H, W) == (1080, 1920):
+    if args.full and args.config == "1080p" and args.fourk and (H, W) == (1080, 1920):
         try:
             fourk = fourk_leg(args, dev_index, dev, rank, world)
         except Exception as ex:                               # a side measurement never loses the line (all ranks take part)
@@ -969,7 +1006,7 @@ def main():
     failed = False
     if rank == 0:
         cpu = None
-        if not args.no_cpu_baseline:
+        if args.full and not args.no_cpu_baseline:
             os.sched_setaffinity(0, all_cpus)                 # the CPU baseline may use every core the job was given
             cpu = cpu_baseline(H, W, spot)
         total_frames = world * F * args.steps
@@ -984,8 +1021,9 @@ def main():
             "steps": args.steps,
             "warmup": args.warmup,
             "ms_per_step": dt / args.steps * 1e3,
+            "full": bool(args.full),
             "host_cpu_s_per_step": host_cpu_s / args.steps,
-            "outputs_identical_across_streams": bool(same_out),
+            "outputs_identical_across_streams": None if same_out is None else bool(same_out),
             "spot_check_vs_oracle": None if cpu is None else cpu.get("spot_check_vs_oracle"),
             "higher_is_better": True,
             "scaling": "weak",
@@ -1027,7 +1065,7 @@ def main():
         spot_res = line["spot_check_vs_oracle"]
         if spot_res is not None and not spot_res.get("ok", False):
             failed = True
-    if not same_out or (host is not None and not host["downloaded_equals_device"]):
+    if same_out is False or (host is not None and not host["downloaded_equals_device"]):
         failed = True
     if world > 1:
         import torch.distributed as dist

@@ -23,8 +23,8 @@ def _run(extra):
 
 
 def test_bench_self_launches_two_ranks():
-    one = _run(["--gpus", "1", "--no-cpu-baseline"])
-    two = _run(["--gpus", "2"])
+    one = _run(["--gpus", "1", "--no-cpu-baseline", "--full"])
+    two = _run(["--gpus", "2", "--full"])
     assert one["n_gpus"] == 1 and two["n_gpus"] == 2
     # the N > 1 line is a complete record: the host-buffer leg ran on every rank (max over ranks) and rank 0 timed the CPU baseline
     assert two["host_buffers"] is not None and two["host_buffers"]["ranks"] == 2 and two["host_buffers"]["downloaded_equals_device"]
@@ -51,6 +51,25 @@ def test_bench_self_launches_two_ranks():
     m = one["roofline"]["matcher"]["in_step"]
     assert m["form"] == 4 and 0 < m["frac_of_fp4_peak"] < m["frac_of_i8_peak"] < 1
     assert one["roofline"]["hbm_copy_measured"]["GBps"] > 1000 and one["roofline"]["hbm_copy_measured"]["lut_pass"]["GBps"] > 1000
+
+
+def test_plain_run_is_the_headline_and_dumps_the_same_outputs(tmp_path):
+    """Without --full the line holds the headline only; --dump-outputs writes the last timed step's results, and the
+    same arguments (any number of steps after a warm-up) give the same arrays."""
+    import numpy as np
+    runs = []
+    for steps in (1, 2):
+        d = _run(["--gpus", "1", "--steps", str(steps), "--dump-outputs", str(tmp_path / str(steps))])
+        assert d["full"] is False and d["steps"] == steps and abs(d["value"] * d["ms_per_step"] / 1e3 - 8) < 1e-6
+        assert d["roofline"] is None and d["cpu_baseline"] is None and d["host_buffers"] is None and d["scenes"] is None
+        files = {p.name: np.load(p) for p in (tmp_path / str(steps)).iterdir()}
+        assert set(files) == {"enhanced.npy", "overlap_ratio.npy", "aclahe_params.npy"}
+        assert files["enhanced.npy"].shape == (8, 270, 480, 3) and files["enhanced.npy"].dtype == np.float32
+        assert files["overlap_ratio.npy"].shape == (8,) and files["aclahe_params.npy"].shape == (8, 2)
+        assert files["enhanced.npy"].min() >= 0 and files["enhanced.npy"].max() <= 255 and files["enhanced.npy"].max() > 0
+        runs.append(files)
+    for name in runs[0]:
+        assert np.array_equal(runs[0][name], runs[1][name], equal_nan=True), name
 
 
 def test_bench_under_torch_distributed_run():
