@@ -238,7 +238,8 @@ int uwip_aclahe_sweep_hist(uwip_ctx *ctx, const uwip_batch_u8 *src, int residual
  *   h_bs (block size) and h_cl (clip limit = the largest of the five knee
  *   indices, used as a clip limit as the reference does); h_knee (may be NULL)
  *   [frames][5].  When 2*CL lies outside the swept grid the BS choice falls
- *   back to the last swept clip limit; uwip_aclahe_auto evaluates it exactly. */
+ *   back to the last swept clip limit; uwip_aclahe_auto evaluates it exactly
+ *   (on the device, whichever form made the choice). */
 int uwip_aclahe_knee(const float *h_xs49, const float *h_ys49, int32_t *index);
 /* The same choice made ON THE DEVICE, from the table the sweep leaves in HBM (no copy to the host, no host computation):
  * one wavefront per (frame, block size) runs the knee stage -- the same source as uwip_aclahe_select
@@ -246,7 +247,8 @@ int uwip_aclahe_knee(const float *h_xs49, const float *h_ys49, int32_t *index);
  * bit for bit -- and one thread per frame the choice of ACLAHE.py:92-125.
  *   d_entropy  device, [frames][5][51] (uwip_aclahe_sweep's output)
  *   d_par      device, [frames][4] int32 = {BS, CL, need_eval, 0}; need_eval = 1 when 2 * CL lies outside the swept grid
- *              (BS then comes from the last swept clip limit; uwip_aclahe_auto_ex evaluates such frames exactly)
+ *              (BS then comes from the last swept clip limit; uwip_aclahe_auto_ex evaluates such frames exactly, in every
+ *              form by the same device kernel, k_aclahe_exact_bs)
  *   d_knee     device, [frames][5] int32, may be NULL: the five knee indices (-1 where curve_fit would raise) */
 int uwip_aclahe_select_device(uwip_ctx *ctx, const float *d_entropy, int frames, int32_t *d_par, int32_t *d_knee);
 /* The persistent host pool uwip_aclahe_select spreads its frames over (one per process, created on first use):
@@ -285,13 +287,15 @@ int uwip_GaussianBlur3(uwip_ctx *ctx, const uwip_batch_u8 *src, const uwip_batch
  *                                  device forces one form process-wide. */
 #define UWIP_ACLAHE_HOST_SELECT 2u
 /*   UWIP_ACLAHE_ASYNC              nothing comes back to the host and the call does not wait: the choice is made on the device,
- *                                  the final per-frame CLAHE is launched from the device-side parameters (the kernels of all
- *                                  five grids are launched over the batch, blocks of frames that chose another grid exit),
- *                                  and a frame whose clip limit leaves the swept grid gets its exact block-size search from a
- *                                  device kernel.  h_bs / h_cl must be NULL; uwip_aclahe_last_params fetches the parameters
- *                                  later (it waits for the stream).  Same image, same parameters as the other forms.  Batches
- *                                  the library gives to the host form (<= 4 frames, UWIP_ACLAHE_SELECT=host) run synchronously
- *                                  under this flag too. */
+ *                                  the exact block-size search is queued behind it unconditionally (blocks of frames whose
+ *                                  clip limit stays in the swept grid exit), and the final per-frame CLAHE is launched from
+ *                                  the device-side parameters (the kernels of all five grids are launched over the batch,
+ *                                  blocks of frames that chose another grid exit).  h_bs / h_cl must be NULL;
+ *                                  uwip_aclahe_last_params fetches the parameters later (it waits for the stream).  Same
+ *                                  image, same parameters as the other forms.  Batches the library gives to the host form
+ *                                  (<= 4 frames, UWIP_ACLAHE_SELECT=host) run synchronously under this flag too.
+ * In every form a frame whose clip limit leaves the swept grid gets its exact block-size search from the same device kernel;
+ * the synchronous forms launch it (and wait for it once more) only when some frame of the batch needs it. */
 #define UWIP_ACLAHE_ASYNC 4u
 int uwip_aclahe_auto_ex(uwip_ctx *ctx, const uwip_batch_u8 *src, const uwip_batch_u8 *dst,
                         int residual_rule, unsigned flags, int32_t *h_bs, int32_t *h_cl);

@@ -439,6 +439,9 @@ def _auto(ctx, t, flags):
     else:
         bs, cl = (C.c_int32 * F)(), (C.c_int32 * F)()
         ctx.call("uwip_aclahe_auto_ex", C.byref(sb), C.byref(db), 0, flags, bs, cl)
+        lbs, lcl = (C.c_int32 * F)(), (C.c_int32 * F)()
+        ctx.call("uwip_aclahe_last_params", lbs, lcl, F)        # the host record reads back what the call returned
+        assert list(lbs) == list(bs) and list(lcl) == list(cl)
     ctx.sync()
     return list(zip(bs, cl)), dst.cpu().numpy()
 
@@ -448,8 +451,9 @@ def test_aclahe_async_equals_synchronous_forms(ctx, orc, shape, monkeypatch):
     """UWIP_ACLAHE_ASYNC (the choice on the device, the final CLAHE launched from device-side parameters, no host wait)
     against the synchronous device-choice form and the host form: same parameters, same bytes.  The frames are made to
     choose different block sizes (contrast / texture vary), so several of the five predicated grids take part; then the
-    out-of-grid path: a forced clip limit of 30 (UWIP_ACLAHE_TEST_FORCE_CL) sends every frame through the exact block-size
-    search -- k_aclahe_exact_bs on the device against the host-ordered CLAHE + entropy runs."""
+    out-of-grid path: a forced clip limit of 30 (UWIP_ACLAHE_TEST_FORCE_CL) sends every frame of every form through the
+    exact block-size search -- k_aclahe_exact_bs, the one implementation -- and the three forms against each other and
+    against the oracle."""
     rows, cols = shape
     rng = np.random.default_rng(5)
     F = 8
@@ -470,21 +474,27 @@ def test_aclahe_async_equals_synchronous_forms(ctx, orc, shape, monkeypatch):
     # the parameters again, against the oracle chain for one frame
     bs, cl = knee_mirror.select_parameters(orc.sweep(orc.gaussian3(frames[0])))
     assert p_async[0] == (bs, cl)
-    # (the hook acts in the device choice; the synchronous forms re-select on the host for such frames, so the check here is
-    # against the oracle: BS = last arg-max of the float16 entropies of CLAHE(blurred plane, 30, g), output = CLAHE(plane, 30, BS))
+    # the hook acts in the device choice and in the host choice alike, so every form takes the exact search; the check is
+    # against the oracle: BS = last arg-max of the float16 entropies of CLAHE(blurred plane, 30, g), output = CLAHE(plane, 30, BS)
     monkeypatch.setenv("UWIP_ACLAHE_TEST_FORCE_CL", "30")
-    ctx.prof_reset(); ctx.prof_enable(True)
-    q_async, r_async = _auto(ctx, t, 1 | 4)
-    prof = ctx.prof_results()
-    ctx.prof_enable(False)
+    forced = {}
+    for flags, form in ((1, "synchronous device choice"), (1 | 2, "host choice"), (1 | 4, "async")):
+        ctx.prof_reset(); ctx.prof_enable(True)
+        forced[flags] = _auto(ctx, t, flags)
+        prof = ctx.prof_results()
+        ctx.prof_enable(False)
+        # k_aclahe_exact_bs is ONE block per flagged frame walking the plane five times -- the worst case of the
+        # stage, reached only by a degenerate fit (none in 1043 tables).  Its cost with EVERY frame flagged
+        # is bounded here (one block per frame and grid, side by side; round 4: one per frame, 3.9 / 63 ms): < 4 ms at
+        # 270 x 480, < 30 ms at 1080p.
+        ms, cnt = prof["k_aclahe_exact_bs"]
+        print(f"k_aclahe_exact_bs ({form}), all {F} frames of {cols}x{rows} flagged: {ms / cnt:.2f} ms")
+        assert ms / cnt < (4.0 if rows < 1000 else 30.0), (form, ms / cnt)
     monkeypatch.delenv("UWIP_ACLAHE_TEST_FORCE_CL")
+    q_async, r_async = forced[1 | 4]
     assert all(c == 30 for _, c in q_async), q_async
-    # k_aclahe_exact_bs is ONE block per flagged frame walking the plane five times -- the worst case of the "no host
-    # wait" stage, reached only by a degenerate fit (none in 1043 tables).  Its cost with EVERY frame flagged
-    # is bounded here (one block per frame and grid, side by side; round 4: one per frame, 3.9 / 63 ms): < 4 ms at 270 x 480, < 30 ms at 1080p.
-    ms, cnt = prof["k_aclahe_exact_bs"]
-    print(f"k_aclahe_exact_bs, all {F} frames of {cols}x{rows} flagged: {ms / cnt:.2f} ms")
-    assert ms / cnt < (4.0 if rows < 1000 else 30.0), ms / cnt
+    assert forced[1][0] == forced[1 | 2][0] == q_async, (forced[1][0], forced[1 | 2][0], q_async)
+    assert np.array_equal(forced[1][1], r_async) and np.array_equal(forced[1 | 2][1], r_async)
     for f in range(F if rows < 1000 else 2):
         filt = orc.gaussian3(frames[f])
         ent = np.array([orc.entropy(orc.clahe(filt, 30.0, g, g)) for g in (2, 4, 8, 16, 32)], np.float32).astype(np.float16)

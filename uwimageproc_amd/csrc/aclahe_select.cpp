@@ -261,18 +261,18 @@ UWIP_API int uwip_aclahe_knee(const float *h_xs49, const float *h_ys49, int32_t 
 
 // h_entropy [frames][5][51] -> per frame BS (block size), CL (clip limit, an index as the reference
 // uses it).  h_knee (optional) [frames][5].  h_need_eval (optional) [frames]: 1 when 2*CL > 50, i.e.
-// the BS choice needs entropies at a clip limit outside the swept grid (the caller supplies them
-// through h_extra [frames][5], used when h_extra_valid[frame] != 0).
+// the BS choice needs entropies at a clip limit outside the swept grid (BS then comes from the last
+// swept clip limit; uwip_aclahe_auto_ex runs the exact search on the device).
 int uwip_aclahe_select_internal(const float *h_entropy, int frames, int32_t *h_bs, int32_t *h_cl, int32_t *h_knee,
-                                int32_t *h_need_eval, const float *h_extra, const int32_t *h_extra_valid);
+                                int32_t *h_need_eval);
 
 UWIP_API int uwip_aclahe_select(const float *h_entropy, int frames, int32_t *h_bs, int32_t *h_cl, int32_t *h_knee)
 {
-    return uwip_aclahe_select_internal(h_entropy, frames, h_bs, h_cl, h_knee, nullptr, nullptr, nullptr);
+    return uwip_aclahe_select_internal(h_entropy, frames, h_bs, h_cl, h_knee, nullptr);
 }
 
 int uwip_aclahe_select_internal(const float *h_entropy, int frames, int32_t *h_bs, int32_t *h_cl, int32_t *h_knee,
-                                int32_t *h_need_eval, const float *h_extra, const int32_t *h_extra_valid)
+                                int32_t *h_need_eval)
 {
     static const int BlockSize[5] = {2, 4, 8, 16, 32};
     if (frames < 0 || (frames > 0 && (!h_entropy || !h_bs || !h_cl))) return UWIP_ERR_INVALID;
@@ -289,13 +289,11 @@ int uwip_aclahe_select_internal(const float *h_entropy, int frames, int32_t *h_b
             }
             if (d < 0) d = 0;
             const bool outside = 2 * d > 50;
-            const bool have_extra = outside && h_extra && h_extra_valid && h_extra_valid[f];
-            if (h_need_eval) h_need_eval[f] = (outside && !have_extra) ? 1 : 0;
+            if (h_need_eval) h_need_eval[f] = outside ? 1 : 0;
             int w = 0;
             float best = 0.f;
             for (int g = 0; g < 5; ++g) {
-                const float e = have_extra ? h_extra[(size_t)f * 5 + g] : tab[(size_t)g * 51 + (outside ? 50 : 2 * d)];
-                const float h = through_half(e);
+                const float h = through_half(tab[(size_t)g * 51 + (outside ? 50 : 2 * d)]);
                 if (g == 0 || h >= best) { best = h; w = g; }      // last maximum wins (ACLAHE.py:118-124)
             }
             h_bs[f] = BlockSize[w];

@@ -1539,25 +1539,38 @@ UWIP_API int uwip_clahe_per_frame(uwip_ctx *ctx, const uwip_batch_u8 *src, const
     return launch_apply_mixed(ctx, src, dst, d_desc, F, max_blocks, max_cells);
 }
 
-// the exact block-size search for the frames uwip_aclahe_select_device flagged (one predicated launch; see k_aclahe_exact_bs)
-static int aclahe_exact_bs_device(uwip_ctx *ctx, const uwip_batch_u8 *src, int32_t *d_par, int residual_rule)
+// the exact block-size search (one predicated launch; see k_aclahe_exact_bs) of the frames the [F][4] record "auto.par"
+// flags, for every form of uwip_aclahe_auto_ex.  Async (h_par = NULL): launched unconditionally behind the device choice.
+// Synchronous (h_par = the host copy of the record): only when some frame is flagged -- the record goes up first when the
+// host made it (upload; field 3, the kernel's arrival counter, is 0), and comes back before the call returns.
+static int aclahe_exact_bs_device(uwip_ctx *ctx, const uwip_batch_u8 *src, int residual_rule, int32_t *h_par, bool upload)
 {
     static const int BlockSize[5] = {2, 4, 8, 16, 32};
     const int F = src->frames;
+    bool any = !h_par;
+    for (int f = 0; !any && f < F; ++f) any = h_par[4 * f + 2] != 0;
+    if (!any) return UWIP_OK;
     ExactGrids G{};
     for (int k = 0; k < 5; ++k) {
         const ClaheGeom g = make_geom(src->rows, src->cols, BlockSize[k], BlockSize[k]);
         G.g[k] = BlockSize[k]; G.tw[k] = g.tw; G.th[k] = g.th; G.pc[k] = g.pc; G.pr[k] = g.pr; G.area[k] = g.area;
         G.inv_tw[k] = g.inv_tw; G.inv_th[k] = g.inv_th; G.lutScale[k] = g.lutScale;
     }
+    int32_t *d_par = (int32_t *)uwip_ws(ctx, "auto.par", sizeof(int32_t) * 4 * (size_t)F);
     uint32_t *d_hists = (uint32_t *)uwip_ws(ctx, "clahe.tilehist", sizeof(uint32_t) * 256 * (size_t)EXACT_TILES * F);
     uint8_t *d_luts = (uint8_t *)uwip_ws(ctx, "sweep.luts", (size_t)256 * 1024 * SWEEP_NCL * F);      // >= 256 * EXACT_TILES * F
     float *d_ent = (float *)uwip_ws(ctx, "auto.exact_ent", sizeof(float) * 5 * (size_t)F);
-    if (!d_hists || !d_luts || !d_ent) return UWIP_ERR_NOMEM;
-    uwip_kscope ks(ctx, "k_aclahe_exact_bs");
-    k_aclahe_exact_bs<<<dim3(F, 5), 512, 0, ctx->stream>>>((const uint8_t *)src->data, src->step, src->frame_stride, src->rows, src->cols, G,
-                                                           residual_rule, d_par, d_hists, d_luts, d_ent);
-    UWIP_HIP(ctx, hipGetLastError());
+    if (!d_par || !d_hists || !d_luts || !d_ent) return UWIP_ERR_NOMEM;
+    if (upload) UWIP_HIP(ctx, hipMemcpyAsync(d_par, h_par, sizeof(int32_t) * 4 * (size_t)F, hipMemcpyHostToDevice, ctx->stream));
+    {
+        uwip_kscope ks(ctx, "k_aclahe_exact_bs");
+        k_aclahe_exact_bs<<<dim3(F, 5), 512, 0, ctx->stream>>>((const uint8_t *)src->data, src->step, src->frame_stride, src->rows,
+                                                               src->cols, G, residual_rule, d_par, d_hists, d_luts, d_ent);
+        UWIP_HIP(ctx, hipGetLastError());
+    }
+    if (!h_par) return UWIP_OK;
+    UWIP_HIP(ctx, hipMemcpyAsync(h_par, d_par, sizeof(int32_t) * 4 * (size_t)F, hipMemcpyDeviceToHost, ctx->stream));
+    UWIP_HIP(ctx, uwip_stream_wait(ctx));
     return UWIP_OK;
 }
 
@@ -1755,10 +1768,10 @@ UWIP_API int uwip_aclahe_sweep(uwip_ctx *ctx, const uwip_batch_u8 *src, int resi
 }
 
 int uwip_aclahe_select_internal(const float *h_entropy, int frames, int32_t *h_bs, int32_t *h_cl, int32_t *h_knee,
-                                int32_t *h_need_eval, const float *h_extra, const int32_t *h_extra_valid);
+                                int32_t *h_need_eval);
 extern "C" int uwip_aclahe_select_device(uwip_ctx *ctx, const float *d_entropy, int frames, int32_t *d_par, int32_t *d_knee);
 
-// C3 + C4 + the final apply in one call: sweep -> (host) parameter choice -> per-frame CLAHE.
+// C3 + C4 + the final apply in one call: sweep -> parameter choice -> exact block-size search -> per-frame CLAHE.
 // This is the whole "aclahe" stage of the pipe.  h_bs / h_cl receive the chosen parameters.
 UWIP_API int uwip_aclahe_auto_ex(uwip_ctx *ctx, const uwip_batch_u8 *img, const uwip_batch_u8 *dst, int residual_rule, unsigned flags,
                                  int32_t *h_bs, int32_t *h_cl)
@@ -1794,88 +1807,61 @@ UWIP_API int uwip_aclahe_auto_ex(uwip_ctx *ctx, const uwip_batch_u8 *img, const 
     }
     const uwip_batch_u8 *src = &filt;
     float *d_ent = (float *)uwip_ws(ctx, "auto.entropy", sizeof(float) * 255 * F);
-    float *h_ent = (float *)uwip_host_ws(ctx, "auto.entropy", sizeof(float) * 255 * F);
-    int32_t *h_par = (int32_t *)uwip_host_ws(ctx, "auto.params", sizeof(int32_t) * 4 * F + sizeof(float) * 5 * F + sizeof(double) * F);
-    if (!d_ent || !h_ent || !h_par) return UWIP_ERR_NOMEM;
+    if (!d_ent) return UWIP_ERR_NOMEM;
     rc = uwip_aclahe_sweep(ctx, src, residual_rule, d_ent);
     if (rc) return rc;
-    int32_t *bs = h_par, *cl = h_par + F, *need = h_par + 2 * F, *valid = h_par + 3 * F;
-    float *extra = (float *)(h_par + 4 * F);
-    double *clip = (double *)(extra + 5 * F);
-    bool any = false;
-    if (!host_select && (flags & UWIP_ACLAHE_ASYNC)) {
-        // nothing comes back to the host: the choice (aclahe_device.hip) and the launch of the final CLAHE from the
-        // device-side parameters (clahe_per_frame_device) are queued behind the sweep, and the call returns
-        int32_t *d_par = (int32_t *)uwip_ws(ctx, "auto.par", sizeof(int32_t) * 4 * (size_t)F);
+    int32_t *d_par = nullptr;
+    if (!host_select) {
+        // the choice on the device (aclahe_device.hip) into the record d_par [F][4] = {BS, CL, need, 0}
+        d_par = (int32_t *)uwip_ws(ctx, "auto.par", sizeof(int32_t) * 4 * (size_t)F);
         if (!d_par) return UWIP_ERR_NOMEM;
         rc = uwip_aclahe_select_device(ctx, d_ent, F, d_par, nullptr);
         if (rc) return rc;
-        rc = aclahe_exact_bs_device(ctx, src, d_par, residual_rule);
-        if (rc) return rc;
-        rc = clahe_per_frame_device(ctx, img, dst, d_par, residual_rule);
-        if (rc) return rc;
-        ctx->aclahe_last_n = F;
-        ctx->aclahe_last_on_device = true;
-        return UWIP_OK;
+        if (flags & UWIP_ACLAHE_ASYNC) {
+            // nothing comes back to the host: the exact search and the launch of the final CLAHE from the device-side
+            // parameters (clahe_per_frame_device) are queued behind the sweep, and the call returns
+            rc = aclahe_exact_bs_device(ctx, src, residual_rule, nullptr, false);
+            if (rc) return rc;
+            rc = clahe_per_frame_device(ctx, img, dst, d_par, residual_rule);
+            if (rc) return rc;
+            ctx->aclahe_last_n = F;
+            ctx->aclahe_last_on_device = true;
+            return UWIP_OK;
+        }
     }
+    // the synchronous forms: the choice in the same record on the host
+    int32_t *par = (int32_t *)uwip_host_ws(ctx, "auto.dpar", sizeof(int32_t) * 4 * (size_t)F);
+    if (!par) return UWIP_ERR_NOMEM;
     if (!host_select) {
-        // the choice on the device (aclahe_device.hip): only {BS, CL, need} per frame come back -- the launch geometry of
-        // the final CLAHE depends on them
-        int32_t *d_par = (int32_t *)uwip_ws(ctx, "auto.par", sizeof(int32_t) * 4 * (size_t)F);
-        int32_t *h_dpar = (int32_t *)uwip_host_ws(ctx, "auto.dpar", sizeof(int32_t) * 4 * (size_t)F);
-        if (!d_par || !h_dpar) return UWIP_ERR_NOMEM;
-        rc = uwip_aclahe_select_device(ctx, d_ent, F, d_par, nullptr);
-        if (rc) return rc;
-        UWIP_HIP(ctx, hipMemcpyAsync(h_dpar, d_par, sizeof(int32_t) * 4 * (size_t)F, hipMemcpyDeviceToHost, ctx->stream));
+        // only the record comes back -- the launch geometry of the final CLAHE depends on it
+        UWIP_HIP(ctx, hipMemcpyAsync(par, d_par, sizeof(int32_t) * 4 * (size_t)F, hipMemcpyDeviceToHost, ctx->stream));
         UWIP_HIP(ctx, uwip_stream_wait(ctx));
-        for (int f = 0; f < F; ++f) {
-            bs[f] = h_dpar[4 * f]; cl[f] = h_dpar[4 * f + 1]; need[f] = h_dpar[4 * f + 2]; valid[f] = 0;
-            any = any || need[f];
-        }
-        if (any) {               // the rare frames whose clip limit leaves the swept grid go through the host form below
-            UWIP_HIP(ctx, hipMemcpyAsync(h_ent, d_ent, sizeof(float) * 255 * F, hipMemcpyDeviceToHost, ctx->stream));
-            UWIP_HIP(ctx, uwip_stream_wait(ctx));
-        }
     } else {
+        float *h_ent = (float *)uwip_host_ws(ctx, "auto.entropy", sizeof(float) * 255 * F);
+        if (!h_ent) return UWIP_ERR_NOMEM;
         UWIP_HIP(ctx, hipMemcpyAsync(h_ent, d_ent, sizeof(float) * 255 * F, hipMemcpyDeviceToHost, ctx->stream));
         UWIP_HIP(ctx, uwip_stream_wait(ctx));            // host decision point (ACLAHE.py:66-129)
-        rc = uwip_aclahe_select_internal(h_ent, F, bs, cl, nullptr, need, nullptr, nullptr);
+        std::vector<int32_t> sel(3 * (size_t)F);         // BS, CL, need
+        rc = uwip_aclahe_select_internal(h_ent, F, sel.data(), sel.data() + F, nullptr, sel.data() + 2 * F);
         if (rc) return ctx->fail(rc, "aclahe select");
-        for (int f = 0; f < F; ++f) { valid[f] = 0; any = any || need[f]; }
-    }
-    if (any) {
-        // clip limit outside the swept grid: evaluate the five block sizes at that clip limit (ACLAHE.py:102-112)
-        static const int BlockSize[5] = {2, 4, 8, 16, 32};
-        uint8_t *tmp = (uint8_t *)uwip_ws(ctx, "auto.tmp", (size_t)src->rows * src->cols);
-        float *d_e1 = (float *)uwip_ws(ctx, "auto.e1", sizeof(float) * 8);
-        if (!tmp || !d_e1) return UWIP_ERR_NOMEM;
+        const int force = uwip_test_force_cl();          // as uwip_aclahe_select_device applies it
         for (int f = 0; f < F; ++f) {
-            if (!need[f]) continue;
-            uwip_batch_u8 one = *src;
-            one.data = (uint8_t *)src->data + (size_t)f * src->frame_stride;
-            one.frames = 1;
-            uwip_batch_u8 t1 = one;
-            t1.data = tmp; t1.step = (size_t)src->cols; t1.frame_stride = (size_t)src->rows * src->cols;
-            for (int g = 0; g < 5; ++g) {
-                rc = uwip_clahe(ctx, &one, &t1, (double)cl[f], BlockSize[g], BlockSize[g], residual_rule);
-                if (rc) return rc;
-                rc = uwip_entropy(ctx, &t1, d_e1 + g);
-                if (rc) return rc;
-            }
-            UWIP_HIP(ctx, hipMemcpyAsync(extra + (size_t)f * 5, d_e1, sizeof(float) * 5, hipMemcpyDeviceToHost, ctx->stream));
-            UWIP_HIP(ctx, uwip_stream_wait(ctx));
-            valid[f] = 1;
+            par[4 * f] = sel[f];
+            par[4 * f + 1] = force >= 0 ? force : sel[F + f];
+            par[4 * f + 2] = force >= 0 ? (2 * force > 50) : sel[2 * F + f];
+            par[4 * f + 3] = 0;
         }
-        rc = uwip_aclahe_select_internal(h_ent, F, bs, cl, nullptr, need, extra, valid);
-        if (rc) return ctx->fail(rc, "aclahe select");
     }
-    for (int f = 0; f < F; ++f) clip[f] = (double)cl[f];
-    if (h_bs) for (int f = 0; f < F; ++f) h_bs[f] = bs[f];
-    if (h_cl) for (int f = 0; f < F; ++f) h_cl[f] = cl[f];
-    rc = uwip_clahe_per_frame(ctx, img, dst, clip, bs, residual_rule);
+    rc = aclahe_exact_bs_device(ctx, src, residual_rule, par, host_select);
     if (rc) return rc;
-    ctx->aclahe_last_host.resize(2 * (size_t)F);
-    for (int f = 0; f < F; ++f) { ctx->aclahe_last_host[2 * f] = bs[f]; ctx->aclahe_last_host[2 * f + 1] = cl[f]; }
+    std::vector<int32_t> bs(F);
+    std::vector<double> clip(F);
+    for (int f = 0; f < F; ++f) { bs[f] = par[4 * f]; clip[f] = (double)par[4 * f + 1]; }
+    if (h_bs) for (int f = 0; f < F; ++f) h_bs[f] = par[4 * f];
+    if (h_cl) for (int f = 0; f < F; ++f) h_cl[f] = par[4 * f + 1];
+    rc = uwip_clahe_per_frame(ctx, img, dst, clip.data(), bs.data(), residual_rule);
+    if (rc) return rc;
+    ctx->aclahe_last_host.assign(par, par + 4 * (size_t)F);
     ctx->aclahe_last_n = F;
     return UWIP_OK;
 }
@@ -1888,17 +1874,18 @@ UWIP_API int uwip_aclahe_last_params(uwip_ctx *ctx, int32_t *h_bs, int32_t *h_cl
     UWIP_REQUIRE(ctx, ctx->aclahe_last_n > 0, "no parameters recorded (no uwip_aclahe_auto_ex yet, or the last one failed)");
     UWIP_REQUIRE(ctx, frames == ctx->aclahe_last_n, "frame count differs from the last uwip_aclahe_auto_ex");
     UWIP_REQUIRE(ctx, h_bs && h_cl, "null output");
+    const int32_t *h = ctx->aclahe_last_host.data();
     if (ctx->aclahe_last_on_device) {
         const int32_t *d_par = (const int32_t *)uwip_ws(ctx, "auto.par", sizeof(int32_t) * 4 * (size_t)frames);
-        int32_t *h = (int32_t *)uwip_host_ws(ctx, "auto.dpar", sizeof(int32_t) * 4 * (size_t)frames);
-        if (!d_par || !h) return UWIP_ERR_NOMEM;
-        UWIP_HIP(ctx, hipMemcpyAsync(h, d_par, sizeof(int32_t) * 4 * (size_t)frames, hipMemcpyDeviceToHost, ctx->stream));
+        int32_t *hp = (int32_t *)uwip_host_ws(ctx, "auto.dpar", sizeof(int32_t) * 4 * (size_t)frames);
+        if (!d_par || !hp) return UWIP_ERR_NOMEM;
+        UWIP_HIP(ctx, hipMemcpyAsync(hp, d_par, sizeof(int32_t) * 4 * (size_t)frames, hipMemcpyDeviceToHost, ctx->stream));
         UWIP_HIP(ctx, uwip_stream_wait(ctx));
-        for (int f = 0; f < frames; ++f) { h_bs[f] = h[4 * f]; h_cl[f] = h[4 * f + 1]; }
-        return UWIP_OK;
+        h = hp;
+    } else {
+        UWIP_REQUIRE(ctx, ctx->aclahe_last_host.size() == 4 * (size_t)frames, "no parameters recorded");
     }
-    UWIP_REQUIRE(ctx, ctx->aclahe_last_host.size() == 2 * (size_t)frames, "no parameters recorded");
-    for (int f = 0; f < frames; ++f) { h_bs[f] = ctx->aclahe_last_host[2 * f]; h_cl[f] = ctx->aclahe_last_host[2 * f + 1]; }
+    for (int f = 0; f < frames; ++f) { h_bs[f] = h[4 * f]; h_cl[f] = h[4 * f + 1]; }
     return UWIP_OK;
 }
 

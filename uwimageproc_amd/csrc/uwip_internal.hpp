@@ -41,7 +41,7 @@ struct uwip_ctx {
     // (UWIP_ACLAHE_ASYNC: workspace "auto.par", [n][4] int32) -- uwip_aclahe_last_params
     int aclahe_last_n = 0;
     bool aclahe_last_on_device = false;
-    std::vector<int32_t> aclahe_last_host;      // [n][2] = BS, CL
+    std::vector<int32_t> aclahe_last_host;      // [n][4] = BS, CL, need, 0 (the layout of "auto.par")
     // the pair list uwip_overlap_match last uploaded (a stream of batches sends the same one every time: no re-upload,
     // and no host wait for the staging buffer)
     std::vector<int32_t> ov_pairs_host;
@@ -119,6 +119,14 @@ inline bool uwip_test_hooks()
 {
     static const bool on = [] { const char *e = std::getenv("UWIP_TEST_HOOKS"); return e && *e == '1'; }();
     return on;
+}
+// UWIP_ACLAHE_TEST_FORCE_CL: the clip limit (a knee index) the aclahe stage's choice gives every frame, -1 when unset.  A
+// knee index >= 26 takes a degenerate fit: the tests force one to reach the exact block-size search.  Read at
+// every call (a test sets it around one call).
+inline int uwip_test_force_cl()
+{
+    const char *e = uwip_test_hooks() ? std::getenv("UWIP_ACLAHE_TEST_FORCE_CL") : nullptr;
+    return e && *e ? std::atoi(e) : -1;
 }
 // hipFuncSetAttribute(MaxDynamicSharedMemorySize) once per (context, kernel)
 int uwip_lds_optin(uwip_ctx *ctx, const char *name, const void *func, size_t bytes);
