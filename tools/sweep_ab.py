@@ -1,5 +1,5 @@
-"""A/B of the sweep's remainder handling in one process is not possible (the mode is read once): run this tool once per
-mode, several times, on the same box:  UWIP_SWEEP_REM=0|1|2 python3 tools/sweep_ab.py   -> ms per 64-frame sweep"""
+"""Times k_clahe_sweep alone: run it several times, alternating the trees to compare, on the same box:
+python3 tools/sweep_ab.py   -> ms per 64-frame sweep (MOTION=1: the moving-scene stream)"""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch
@@ -18,4 +18,4 @@ for _ in range(5):
     aclahe.sweep(ctx, v)
 ctx.sync()
 ms, cnt = ctx.prof_results()["k_clahe_sweep"]
-print(f"rem {os.environ.get('UWIP_SWEEP_REM', '1')} int {os.environ.get('UWIP_SWEEP_INT', '1')} motion {os.environ.get('MOTION', '')}: {ms / 5:.3f} ms per 64-frame sweep", flush=True)
+print(f"motion {os.environ.get('MOTION', '')}: {ms / 5:.3f} ms per 64-frame sweep", flush=True)

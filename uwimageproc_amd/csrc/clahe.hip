@@ -207,7 +207,7 @@ constexpr int TH_BP_WORDS = 128 * TH_BP_SLOTS;
 // (a per-lane mask bit shifted into the increment: no per-pixel branch); reflect-101 padding columns and rows as in the
 // replica form.  The replica form spent 90 / 112 us per 64 frames on those grids (4 pixels per load, 16 lanes per replica),
 // against 40 us of the slot-keyed form on the aligned grids.
-// Measured per 64 frames of 1080p (tools/tilehist_only.py, UWIP_TILEHIST_GENERAL=0|1): 16 x 16 grid (121 x 68 tiles) 86 -> 67 us;
+// Measured per 64 frames of 1080p (tools/tilehist_only.py, replica form -> FORM 2): 16 x 16 grid (121 x 68 tiles) 86 -> 67 us;
 // 32 x 32 grid (61 x 34 tiles = 2074 pixels: 33 pixels per lane against an 8 KB zero + 2048-slot flush per wave, three row
 // passes of 16 rows for 34 rows) 107 -> 157 us: those stay with the replica form.
 constexpr int TH_G_MIN = 4096;            // pixels per tile from which the 8 KB zero + flush of the slot-keyed layout pays
@@ -804,7 +804,7 @@ __global__ __launch_bounds__(SWEEP_THREADS) void k_clahe_sweep(const uint8_t *__
                                                      int items_per_block,
                                                      uint32_t *__restrict__ out_hist /*[F][51][256]*/,
                                                      size_t out_fs, const uint32_t *__restrict__ tile_max /*[F][tiles]*/,
-                                                     ClipList cl, int rem_mode)
+                                                     ClipList cl)
 {
     extern __shared__ __attribute__((aligned(16))) uint32_t s_sweep[];
     uint32_t *s_pack = s_sweep;                                   // [SWEEP_GROUP][256]
@@ -897,36 +897,9 @@ __global__ __launch_bounds__(SWEEP_THREADS) void k_clahe_sweep(const uint8_t *__
         // ceil(rem / 64) waves run the last round instead of all eight with a few lanes each (a 61 x 34 cell of the 32 x 32
         // grid has 4 whole groups + 26 pixels: 5 rounds for every wave became 4 + one wave's).
         const int nfull = npix / SWEEP_THREADS, rem = npix - nfull * SWEEP_THREADS;
-        // A SMALL remainder is not given a round of its own at all (the block would wait a whole round for one wave): its
-        // rem x nl evaluations -- nl per pixel: the distinct limits, + the separate G evaluation -- are dealt one per thread,
-        // a thread = (pixel, evaluation).  Same counts in the same counters.
-        const int nl = (nd == SWEEP_GROUP ? SWEEP_GROUP : nd) + (g_sep ? 1 : 0);
-        const bool rem_spread = rem_mode == 2 && rem > 0 && rem * nl <= 4 * SWEEP_THREADS;
-        if (rem_spread) {
-            for (int idx = tid; idx < rem * nl; idx += SWEEP_THREADS) {
-                const int pp = idx / nl, e = idx - pp * nl;
-                int x, y;
-                locate(nfull * SWEEP_THREADS + pp, x, y);
-                const uint32_t v = pix_at(x, y);
-                const float txf = (float)x * inv_tw - 0.5f;
-                const float xa = txf - floorf(txf), xa1 = 1.0f - xa;
-                const float tyf = (float)y * inv_th - 0.5f;
-                const float ya = tyf - floorf(tyf), ya1 = 1.0f - ya;
-                const uint32_t *pack_v = s_pack + v;
-                if (g_sep && e == nl - 1) { atomicAdd(&s_g[sweep_eval(pack_v[0], xa1, xa, ya1, ya)], 65536u); continue; }
-                const uint32_t o = sweep_eval(pack_v[e * 256], xa1, xa, ya1, ya);
-                if (nd == SWEEP_GROUP || e < ns) atomicAdd(&my_hist[(e >> 1) * 256 + o], (e & 1) ? 65536u : 1u);
-                else {                                              // e == ns: the last distinct limit -> tail histogram
-                    atomicAdd(&s_tail[(ns >> 1) * 256 + o], (ns & 1) ? 65536u : 1u);
-                    if (g_last) atomicAdd(&s_g[o], 65536u);
-                }
-            }
-        }
-        // rem_mode 0 (diagnostic): the remainder by the spread mapping too, i.e. every wave runs the last round with a few lanes
-        const int rem_pos = rem_mode == 0 ? pix_of(0) : tid;
-        const int ntot = nfull + ((!rem_spread && rem_pos < rem) ? 1 : 0);
+        const int ntot = nfull + (tid < rem ? 1 : 0);
         int t = 0;
-        if (ntot > 0) { locate(nfull > 0 ? pix_of(0) : rem_pos, xn, yn); vnext = pix_at(xn, yn); }
+        if (ntot > 0) { locate(nfull > 0 ? pix_of(0) : tid, xn, yn); vnext = pix_at(xn, yn); }
         // a thread's next pixel is SWEEP_THREADS further along the cell: step (x, y) instead of dividing again
         const int dq = SWEEP_THREADS / w, dr = SWEEP_THREADS - dq * w;     // wave-uniform
         for (; t < ntot;) {
@@ -938,7 +911,7 @@ __global__ __launch_bounds__(SWEEP_THREADS) void k_clahe_sweep(const uint8_t *__
                     xn += dr; yn += dq;
                     if (xn >= ci.x1) { xn -= w; yn++; }
                 } else {
-                    locate(nfull * SWEEP_THREADS + rem_pos, xn, yn);      // the remainder pixel
+                    locate(nfull * SWEEP_THREADS + tid, xn, yn);          // the remainder pixel
                 }
                 vnext = pix_at(xn, yn);
             }
@@ -1033,6 +1006,13 @@ bool aligned_for(const uwip_batch_u8 *b, size_t a)
     return ((uintptr_t)b->data % a == 0) && (b->step % a == 0) && (b->frames <= 1 || b->frame_stride % a == 0);
 }
 
+// the big-tile (slot-keyed, FORM 1) tile histogram applies: tiles of >= TH_BP_MIN pixels whose rows are 16-byte aligned runs
+bool big_tile_ok(const uwip_batch_u8 *src, const ClaheGeom &g)
+{
+    return (long long)g.tw * g.th >= TH_BP_MIN && (g.tw & 15) == 0 && g.tw * g.gx == g.cols && g.tw < (1 << 17) &&
+           ((reinterpret_cast<uintptr_t>(src->data) | src->step | src->frame_stride) & 15u) == 0;
+}
+
 int launch_tilehist(uwip_ctx *ctx, const uwip_batch_u8 *src, const ClaheGeom &g, const int *d_frame_map,
                     int nf, uint32_t *d_hists, const int *d_nf = nullptr)
 {
@@ -1045,8 +1025,7 @@ int launch_tilehist(uwip_ctx *ctx, const uwip_batch_u8 *src, const ClaheGeom &g,
     // (saturated / black) tile carries the even bin's counter into the odd bin's.  TH_BP_PART_MAX keeps a margin for
     // the rounding of rows_per_part (one more row of < 2^17 columns); wider tiles take the 32-bit replica form.
     constexpr long long TH_BP_PART_MAX = 3ll << 17;                   // 393 216 pixels
-    const bool bp = (long long)g.tw * g.th >= TH_BP_MIN && (g.tw & 15) == 0 && g.tw * g.gx == g.cols && g.tw < (1 << 17) &&
-                    ((reinterpret_cast<uintptr_t>(src->data) | src->step | src->frame_stride) & 15u) == 0;
+    const bool bp = big_tile_ok(src, g);
     // FORM 2: any other tile of >= TH_G_MIN pixels in an image at least 16 columns wide (the tail unit of a row is loaded
     // ending at the tile's last in-image column)
     const bool bpg = !bp && (long long)g.tw * g.th >= TH_G_MIN && g.cols >= 16 && g.tw >= 16 && g.tw < (1 << 17);
@@ -1065,11 +1044,10 @@ int launch_tilehist(uwip_ctx *ctx, const uwip_batch_u8 *src, const ClaheGeom &g,
     if (split > 1) UWIP_HIP(ctx, hipMemsetAsync(d_hists, 0, sizeof(uint32_t) * 256 * (size_t)tiles * nf, ctx->stream));
     dim3 grid((unsigned)((tiles * split + 3) / 4), (unsigned)nf);
     uwip_kscope ks(ctx, "k_clahe_tilehist");
-    static const bool no_general = [] { const char *e = std::getenv("UWIP_TILEHIST_GENERAL"); return e && *e == '0'; }();    // A/B
     if (bp)
         k_clahe_tilehist<1><<<grid, 256, 0, ctx->stream>>>((const uint8_t *)src->data, src->step, src->frame_stride, g.rows, g.cols,
                                                            g.gx, g.tw, g.th, split, rpp, d_frame_map, d_hists, tiles, d_nf);
-    else if (bpg && !no_general)
+    else if (bpg)
         k_clahe_tilehist<2><<<grid, 256, 0, ctx->stream>>>((const uint8_t *)src->data, src->step, src->frame_stride, g.rows, g.cols,
                                                            g.gx, g.tw, g.th, split, rpp, d_frame_map, d_hists, tiles, d_nf);
     else
@@ -1092,23 +1070,18 @@ int launch_lut(uwip_ctx *ctx, const ClaheGeom &g, const uint32_t *d_hists, const
 // tile histograms + LUT rows in one launch (k_clahe_band) where the geometry allows and the big-tile form does not apply
 bool band_ok(const uwip_batch_u8 *src, const ClaheGeom &g)
 {
-    static const bool off = [] { const char *e = std::getenv("UWIP_CLAHE_BAND"); return e && *e == '0'; }();      // A/B
-    const bool bp = (long long)g.tw * g.th >= TH_BP_MIN && (g.tw & 15) == 0 && g.tw * g.gx == g.cols && g.tw < (1 << 17) &&
-                    ((reinterpret_cast<uintptr_t>(src->data) | src->step | src->frame_stride) & 15u) == 0;
     // tw >= 2: the column -> tile division is a multiply-high by floor(2^32 / tw) + 1, which does not exist for tw = 1
-    return !off && !bp && g.tw >= 2 && g.cols >= 16 && g.cols <= 8192 && (long long)g.tw * g.th < 65536 && g.gy <= 4096;
+    return !big_tile_ok(src, g) && g.tw >= 2 && g.cols >= 16 && g.cols <= 8192 && (long long)g.tw * g.th < 65536 && g.gy <= 4096;
 }
 
 int launch_band(uwip_ctx *ctx, const uwip_batch_u8 *src, const ClaheGeom &g, const int *d_frame_map, int nf, const ClipList &cl,
                 const int *d_frame_clip, int rule, uint8_t *d_luts, uint32_t *d_tile_max, const int *d_nf = nullptr)
 {
     // tiles per block: as many as fill one 64-unit chunk (1024 columns: every lane of the block's eight waves busy), at most
-    // 16 (33 KB of LDS: four blocks per CU).  Measured per 64 frames of 1080p (tools/tilehist_only.py, UWIP_BAND_TPB): 16 x 16
+    // 16 (33 KB of LDS: four blocks per CU).  Measured per 64 frames of 1080p (tools/tilehist_only.py): 16 x 16
     // grid (121-pixel tiles) 8 tiles per block 43.9 us, 16 (the whole row) 48.5; 32 x 32 grid (61-pixel tiles) 16 per block
     // 63.1, 32 (the whole row, 66 KB) 66.5, 8 (half the lanes idle) 99.5.
-    static const int env_tpb = [] { const char *e = std::getenv("UWIP_BAND_TPB"); return e && *e ? std::atoi(e) : 0; }();
-    int tpb = std::min(g.gx, std::min(16, std::max(1, 1024 / g.tw)));
-    if (env_tpb > 0) tpb = std::min(env_tpb, g.gx);
+    const int tpb = std::min(g.gx, std::min(16, std::max(1, 1024 / g.tw)));
     const int nparts = (g.gx + tpb - 1) / tpb;
     const int part_cols = std::min(tpb * g.tw, g.cols);
     const int nu = (part_cols + 15) / 16 + 1;                          // a part's columns need not start on a unit boundary
@@ -1742,15 +1715,11 @@ UWIP_API int uwip_aclahe_sweep_hist(uwip_ctx *ctx, const uwip_batch_u8 *src, int
         dim3 grid(uwip_cdiv(nitems, ipb), SWEEP_NCL / SWEEP_GROUP, (unsigned)F);
         uwip_kscope ks(ctx, "k_clahe_sweep");
         const size_t sweep_lds = sizeof(uint32_t) * SWEEP_LDS_WORDS;
-        // how a cell's npix mod 512 pixels are walked (UWIP_SWEEP_REM; same box, 64-frame sweeps, tools/sweep_ab.py): 0 = round 2's
-        // spread round, every wave with a few lanes: 7.93 ms; 1 = one contiguous round, one wave's worth: 7.67 ms (default);
-        // 2 = small remainders as (pixel, evaluation) threads: 7.78 ms
-        static const int rem_mode = [] { const char *e = getenv("UWIP_SWEEP_REM"); return e && *e >= '0' && *e <= '2' ? *e - '0' : 1; }();
         rc = uwip_lds_optin(ctx, "k_clahe_sweep", (const void *)k_clahe_sweep, sweep_lds);
         if (rc) return rc;
         k_clahe_sweep<<<grid, SWEEP_THREADS, sweep_lds, ctx->stream>>>((const uint8_t *)src->data, src->step, src->frame_stride, g.gx,
                                                      g.gy, g.inv_tw, g.inv_th, d_luts, d_items, nitems, ipb,
-                                                     d_out + (size_t)gi * SWEEP_NCL * 256, out_fs, d_tmax, cl, rem_mode);
+                                                     d_out + (size_t)gi * SWEEP_NCL * 256, out_fs, d_tmax, cl);
         UWIP_HIP(ctx, hipGetLastError());
     }
     {

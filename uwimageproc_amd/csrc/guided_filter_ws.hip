@@ -149,17 +149,18 @@ struct SolveRow<NP, true> {
 // scanning its own 256; the scans meet in LDS -- a window that straddles the two halves adds the left wave's row total --
 // behind one workgroup barrier per phase.  Useful columns per lane-column rise from 176 / 256 to 432 / 512: at 1920
 // columns 5 strips x 512 instead of 11 x 256 (-9 % of all work), at 3840 columns 9 x 512 instead of 22 x 256 (-18 %).
-// PTAB (PU8 only): p through a 256-entry float64 table per plane in LDS (4 KB at NP = 2) -- or, PTAB = false, computed per
-// sample as max(1 - (m - mn) * c_ip, tmin) with c_ip = 1 / ((mx - mn) B_ip): a conversion, an fma and a max instead of an
-// LDS gather, within 2 ulp of the table's two divisions (the filter is compared at 1e-9), and 25.6 instead of 29.7 KB of
-// LDS per wave: four solve waves then leave a CU 56 KB, room for one 52 KB block of k_clahe_sweep (with the table they
-// left 41 KB and the VALU-bound sweep could not join the latency-bound solve on a CU; DESIGN.md section 5, co-residency).
-template <int NP, bool VEC, bool PU8, bool C3, int NW, bool PTAB = true>
+// With PU8, p is computed per sample as max(1 - (m - mn) * c_ip, tmin) with c_ip = 1 / ((mx - mn) B_ip): a conversion, an
+// fma and a max, within 2 ulp of k_transmission's two divisions (the filter is compared at 1e-9).  No p table in LDS: 25.6
+// KB of LDS per wave, so four solve waves leave a CU 56 KB, room for one 52 KB block of k_clahe_sweep (a 256-entry float64
+// table per plane took the wave to 29.7 KB and left 41 KB: the VALU-bound sweep could not join the latency-bound solve on a
+// CU; DESIGN.md section 5, co-residency).
+// A block solves the NP p planes of one frame: blockIdx z (after xcd_decode) is the frame.
+template <int NP, bool VEC, bool PU8, bool C3, int NW>
 __global__ __launch_bounds__(64 * NW) void k_gf_ws_solve(const uint8_t *__restrict__ guide, size_t step, size_t fs,
                                                     const int *__restrict__ gnorm, int gnorm_stride,
                                                     const double *__restrict__ P /*[F][NP][H][W]*/,
                                                     double *__restrict__ AB /*[F*NP][4][H][W]: column prefix sums of a, b*/,
-                                                    int H, int W, int r, double eps, int TS, int rpc, int fdiv, uint3 nb,
+                                                    int H, int W, int r, double eps, int TS, int rpc, uint3 nb,
                                                     uwip_gf_pu8 pu8)
 {
 #pragma clang fp contract(fast)
@@ -170,7 +171,6 @@ __global__ __launch_bounds__(64 * NW) void k_gf_ws_solve(const uint8_t *__restri
     __shared__ double2 s_d2[NW * NP * 2 * 4 * 64];
     __shared__ uint32_t s_tu[NW][12];          // row totals of a wave's nine integer planes
     __shared__ double s_td[NW][NP * 4];        // ... and of its 4 NP float64 planes
-    __shared__ double s_ptab[PU8 && PTAB ? NP * 256 : 1];
     unsigned bx, by, bz;
     if (!xcd_decode(nb.x, nb.y, nb.z, bx, by, bz)) return;
     StripGeom sg;
@@ -178,32 +178,21 @@ __global__ __launch_bounds__(64 * NW) void k_gf_ws_solve(const uint8_t *__restri
     const int wv = NW > 1 ? (int)(threadIdx.x >> 6) : 0;
     // hand-over between the phases of a row: the LDS rows are private to the wave (NW = 1) or shared by the block
     auto sync = [&]() { if constexpr (NW > 1) __syncthreads(); else wave_lds_fence(); };
-    // bz counts groups of NP p-planes; fdiv of them share a frame (fdiv = np / NP)
-    const int l = sg.l, zg = bz, f = zg / fdiv;
+    const int l = sg.l, f = bz;
     const size_t n = (size_t)H * W;
     const int mn = gnorm[(size_t)f * gnorm_stride], mx = gnorm[(size_t)f * gnorm_stride + 1];
     const uint32_t fillw = (uint32_t)mn * 0x01010101u;
     const uint8_t *gf = guide + (size_t)f * fs;
-    const double *pin = P + (size_t)zg * NP * n;
+    const double *pin = P + (size_t)f * NP * n;
     double p_out = 0.0;         // PU8: p where the window leaves the image
     bool cin[4] = {true, true, true, true};
-    const int ip0 = (zg - f * fdiv) * NP;     // first of this block's p planes inside the frame
-    double pc[NP];              // !PTAB: c_ip
+    double pc[NP];              // PU8: c_ip
 #pragma unroll
     for (int ip = 0; ip < NP; ++ip) pc[ip] = 0.0;
     if (PU8) {
-        if constexpr (PTAB) {
-            for (int idx = (int)threadIdx.x; idx < NP * 256; idx += 64 * NW) {
-                const int ip = idx >> 8, v = idx & 255;
-                const double B = pu8.sc[(size_t)f * pu8.sc_stride + pu8.b_off + ip0 + ip];
-                const double q = ((double)(v - mn) / (double)(mx - mn)) / B;
-                s_ptab[idx] = fmax(1.0 - q, pu8.tmin);
-            }
-        } else {
 #pragma unroll
-            for (int ip = 0; ip < NP; ++ip)
-                pc[ip] = 1.0 / ((double)(mx - mn) * pu8.sc[(size_t)f * pu8.sc_stride + pu8.b_off + ip0 + ip]);
-        }
+        for (int ip = 0; ip < NP; ++ip)
+            pc[ip] = 1.0 / ((double)(mx - mn) * pu8.sc[(size_t)f * pu8.sc_stride + pu8.b_off + ip]);
         p_out = fmax(1.0 - 0.0, pu8.tmin);
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
@@ -274,7 +263,7 @@ __global__ __launch_bounds__(64 * NW) void k_gf_ws_solve(const uint8_t *__restri
         if constexpr (PU8) {
             R.g = *reinterpret_cast<const u32x3 *>(g_lane + (size_t)yy * step);
 #pragma unroll
-            for (int ip = 0; ip < NP; ++ip) R.m[ip] = *reinterpret_cast<const uint32_t *>(m_lane + ((size_t)(ip0 + ip) * H + yy) * W);
+            for (int ip = 0; ip < NP; ++ip) R.m[ip] = *reinterpret_cast<const uint32_t *>(m_lane + ((size_t)ip * H + yy) * W);
         } else if constexpr (VEC) {
             {
                 const uint32_t *q = reinterpret_cast<const uint32_t *>(g_lane + (size_t)yy * step);
@@ -317,8 +306,7 @@ __global__ __launch_bounds__(64 * NW) void k_gf_ws_solve(const uint8_t *__restri
 #pragma unroll
             for (int ip = 0; ip < NP; ++ip) {
                 double pv;
-                if constexpr (PU8 && PTAB) pv = (rin && cin[j]) ? s_ptab[ip * 256 + ((R.m[ip] >> (8 * j)) & 255u)] : p_out;
-                else if constexpr (PU8) {
+                if constexpr (PU8) {
                     const double pt = fmax(fma(-(double)((int)((R.m[ip] >> (8 * j)) & 255u) - mn), pc[ip], 1.0), pu8.tmin);
                     pv = (rin && cin[j]) ? pt : p_out;
                 }
@@ -469,7 +457,7 @@ __global__ __launch_bounds__(64 * NW) void k_gf_ws_solve(const uint8_t *__restri
                 const size_t i = (size_t)y * W + sx0 + j;
 #pragma unroll
                 for (int ip = 0; ip < NP; ++ip) {
-                    double *o = AB + ((size_t)zg * NP + ip) * 4 * n + i;
+                    double *o = AB + ((size_t)f * NP + ip) * 4 * n + i;
 #pragma unroll
                     for (int q = 0; q < 4; ++q)
                         if (s_act[j]) o[(size_t)q * n] = cs[j][ip][q];
@@ -484,7 +472,7 @@ __global__ __launch_bounds__(64 * NW) void k_gf_ws_solve(const uint8_t *__restri
                 const size_t i = (size_t)y * W + sg.x0 + jj;
 #pragma unroll
                 for (int ip = 0; ip < NP; ++ip) {
-                    double *o = AB + ((size_t)zg * NP + ip) * 4 * n + i;
+                    double *o = AB + ((size_t)f * NP + ip) * 4 * n + i;
 #pragma unroll
                     for (int q = 0; q < 4; ++q) {
                         if (VEC) {
@@ -731,6 +719,21 @@ __global__ __launch_bounds__(64 * NW) void k_gf_ws_final(const double *__restric
     }
 }
 
+// One (NP, VEC, PU8) form of the solve: two waves per strip (nw = 2, aligned path only), else one wave with the 3-column
+// (c3) or the 4-column solve mapping.
+template <int NP, bool VEC, bool PU8, class... Args>
+void launch_solve(int nw, bool c3, unsigned grid, hipStream_t stream, Args... args)
+{
+    if constexpr (VEC) {
+        if (nw == 2) {
+            k_gf_ws_solve<NP, VEC, PU8, false, 2><<<grid, 128, 0, stream>>>(args...);
+            return;
+        }
+    }
+    if (c3) k_gf_ws_solve<NP, VEC, PU8, true, 1><<<grid, 64, 0, stream>>>(args...);
+    else k_gf_ws_solve<NP, VEC, PU8, false, 1><<<grid, 64, 0, stream>>>(args...);
+}
+
 }  // namespace
 
 // Launches the two kernels.  guide: 3-channel u8 frames; gnorm[f*gstride + {0,1}] = the frame's min / max guide
@@ -768,14 +771,10 @@ int uwip_gf_wave_strip(uwip_ctx *ctx, const uint8_t *guide, size_t step, size_t 
         if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, threads, 0) != hipSuccess || per_cu < 1) per_cu = 8;
         return (double)per_cu * cus;
     };
-    const char *env_split = getenv("UWIP_GF_SPLIT");
-    const bool split = np == 2 && env_split && atoi(env_split) > 0;   // two one-plane solves instead of a fused one
-    const int knp = split ? 1 : np;
-    const unsigned zs = (unsigned)F * (np / knp);
     // (occupancy query only: the 3-column and 4-column solve mappings differ by a few registers, both one wave per SIMD)
-    const void *ksolve = pu8 ? (knp == 2 ? (const void *)k_gf_ws_solve<2, true, true, true, 1> : (const void *)k_gf_ws_solve<1, true, true, true, 1>)
-                       : knp == 2 ? (vec ? (const void *)k_gf_ws_solve<2, true, false, true, 1> : (const void *)k_gf_ws_solve<2, false, false, true, 1>)
-                                  : (vec ? (const void *)k_gf_ws_solve<1, true, false, true, 1> : (const void *)k_gf_ws_solve<1, false, false, true, 1>);
+    const void *ksolve = pu8 ? (const void *)k_gf_ws_solve<2, true, true, true, 1>
+                       : np == 2 ? (vec ? (const void *)k_gf_ws_solve<2, true, false, true, 1> : (const void *)k_gf_ws_solve<2, false, false, true, 1>)
+                                 : (vec ? (const void *)k_gf_ws_solve<1, true, false, true, 1> : (const void *)k_gf_ws_solve<1, false, false, true, 1>);
     // Two waves per strip (512 columns; aligned path only) cover the width with fewer lane-columns -- 1920 columns, r = 40:
     // 5 x 512 against 11 x 256 (-9 %), 3840 columns: 9 x 512 against 22 x 256 (-18 %) -- and measure within 1 % of the
     // one-wave form at 1080p and -4.5 % (solve only) at 4K: the two waves meet at a barrier twice per row and the kernel is
@@ -793,55 +792,31 @@ int uwip_gf_wave_strip(uwip_ctx *ctx, const uint8_t *guide, size_t step, size_t 
     int c = 1;
     {
         const int cmax = std::max(1, H / D);
-        const char *e = getenv("UWIP_GF_CHUNKS");
-        if (e && atoi(e) > 0) c = std::min(atoi(e), cmax);
-        else {
-            const double slots = slots_of(ksolve);
-            double best_cost = 1e300;
-            for (int t = 1; t <= 16 && t <= cmax; ++t) {
-                const double waves = (double)strips_s * nw * zs * t;
-                const double rounds = std::max(1.0, std::ceil(waves / slots));
-                const double cost = rounds * ((double)((H + t - 1) / t) + 2.0 * r);
-                if (cost < best_cost * 0.97) { best_cost = cost; c = t; }
-            }
+        const double slots = slots_of(ksolve);
+        double best_cost = 1e300;
+        for (int t = 1; t <= 16 && t <= cmax; ++t) {
+            const double waves = (double)strips_s * nw * F * t;
+            const double rounds = std::max(1.0, std::ceil(waves / slots));
+            const double cost = rounds * ((double)((H + t - 1) / t) + 2.0 * r);
+            if (cost < best_cost * 0.97) { best_cost = cost; c = t; }
         }
     }
     int rpc = (H + c - 1) / c;
     if (rpc < D) rpc = D;
     {
-        const uint3 nb = make_uint3(strips_s, uwip_cdiv(H, rpc), zs);
+        const uint3 nb = make_uint3(strips_s, uwip_cdiv(H, rpc), (unsigned)F);
         const unsigned grid = 8u * ((nb.x * nb.y * nb.z + 7u) / 8u);
         uwip_kscope ks(ctx, "k_gf_ws_solve");
-        const int fdiv = np / knp;
         const uwip_gf_pu8 none{};
         const uwip_gf_pu8 &pa = pu8 ? *pu8 : none;
-#define UWIP_GF_SOLVE(NPV, VECV, PU8V, C3V, NWV)                                                                                     \
-    k_gf_ws_solve<NPV, VECV, PU8V, C3V, NWV><<<grid, 64 * NWV, 0, ctx->stream>>>(guide, step, fs, gnorm, gstride, P, AB, H, W, r, eps, \
-                                                                               TSs, rpc, fdiv, nb, pa)
-#define UWIP_GF_SOLVE_NT(NPV, C3V, NWV)                                                                                              \
-    k_gf_ws_solve<NPV, true, true, C3V, NWV, false><<<grid, 64 * NWV, 0, ctx->stream>>>(guide, step, fs, gnorm, gstride, P, AB, H, W, r, \
-                                                                                      eps, TSs, rpc, fdiv, nb, pa)
         const bool c3 = nw == 1 && TSs <= 192;
-        // the 8-bit p source without its LDS table (the default; UWIP_GF_PTAB=1 keeps the table: A/B)
-        static const bool ptab = [] { const char *e = getenv("UWIP_GF_PTAB"); return e && atoi(e) > 0; }();
+#define UWIP_GF_SOLVE(NPV, VECV, PU8V) \
+    launch_solve<NPV, VECV, PU8V>(nw, c3, grid, ctx->stream, guide, step, fs, gnorm, gstride, P, AB, H, W, r, eps, TSs, rpc, nb, pa)
         if (diag_only == 2) {
             // diagnostic: the second kernel alone (tools/corun_matrix.py)
-        } else if (pu8 && knp == 1 && !ptab) {
-            if (nw == 2) UWIP_GF_SOLVE_NT(1, false, 2); else if (c3) UWIP_GF_SOLVE_NT(1, true, 1); else UWIP_GF_SOLVE_NT(1, false, 1);
-        } else if (pu8 && !ptab) {
-            if (nw == 2) UWIP_GF_SOLVE_NT(2, false, 2); else if (c3) UWIP_GF_SOLVE_NT(2, true, 1); else UWIP_GF_SOLVE_NT(2, false, 1);
-        } else if (pu8 && knp == 1) {
-            if (nw == 2) UWIP_GF_SOLVE(1, true, true, false, 2); else if (c3) UWIP_GF_SOLVE(1, true, true, true, 1); else UWIP_GF_SOLVE(1, true, true, false, 1);
-        } else if (pu8) {
-            if (nw == 2) UWIP_GF_SOLVE(2, true, true, false, 2); else if (c3) UWIP_GF_SOLVE(2, true, true, true, 1); else UWIP_GF_SOLVE(2, true, true, false, 1);
-        } else if (knp == 2) {
-            if (vec) { if (nw == 2) UWIP_GF_SOLVE(2, true, false, false, 2); else if (c3) UWIP_GF_SOLVE(2, true, false, true, 1); else UWIP_GF_SOLVE(2, true, false, false, 1); }
-            else { if (c3) UWIP_GF_SOLVE(2, false, false, true, 1); else UWIP_GF_SOLVE(2, false, false, false, 1); }
-        } else {
-            if (vec) { if (nw == 2) UWIP_GF_SOLVE(1, true, false, false, 2); else if (c3) UWIP_GF_SOLVE(1, true, false, true, 1); else UWIP_GF_SOLVE(1, true, false, false, 1); }
-            else { if (c3) UWIP_GF_SOLVE(1, false, false, true, 1); else UWIP_GF_SOLVE(1, false, false, false, 1); }
-        }
-#undef UWIP_GF_SOLVE_NT
+        } else if (pu8) UWIP_GF_SOLVE(2, true, true);       // uwip_gf_pu8_ok: np = 2, aligned
+        else if (np == 2) { if (vec) UWIP_GF_SOLVE(2, true, false); else UWIP_GF_SOLVE(2, false, false); }
+        else { if (vec) UWIP_GF_SOLVE(1, true, false); else UWIP_GF_SOLVE(1, false, false); }
 #undef UWIP_GF_SOLVE
     }
     {
@@ -863,8 +838,6 @@ int uwip_gf_wave_strip(uwip_ctx *ctx, const uint8_t *guide, size_t step, size_t 
         if (rec) UWIP_REQUIRE(ctx, vec && rec->sc, "fused recovery needs the aligned path");
         const int nchain = std::min(D, H);
         int groups = (int)std::ceil(4.0 * slots_of(kfinal, 64 * nwf) / ((double)strips_f * Z));
-        const char *e = getenv("UWIP_GF_GROUPS");
-        if (e && atoi(e) > 0) groups = atoi(e);
         groups = std::max(1, std::min(groups, nchain));
         const int spw = (nchain + groups - 1) / groups;
         const uint3 nb = make_uint3(strips_f, uwip_cdiv(nchain, spw), Z);

@@ -253,12 +253,6 @@ __global__ __launch_bounds__(256) void k_apply_lut(uint8_t *__restrict__ data, S
     }
 }
 
-__global__ void k_identity_lut(uint8_t *lut, size_t n)
-{
-    size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) lut[i] = (uint8_t)(i & 255);
-}
-
 // -------------------------------------------------------------------------
 struct SpanPlan {
     SpanGeom g;

@@ -985,9 +985,8 @@ __global__ __launch_bounds__(64) void k_ov_describe(const float *__restrict__ Lt
 }
 
 // ---- brute-force Hamming kNN(2): dense q x t dot products on i8 MFMA -------------------------------------
-// popcount(a xor b) = |a| + |b| - 2 a.b with a, b in {0,1}^512 held as bytes.
-// Block = 4 waves = 64 queries; train descriptors staged through LDS 64 at a time (row stride 528 B:
-// the 16 lanes of a ds_read_b128 group then fall on 16 different 16-byte slots).
+// popcount(a xor b) = |a| + |b| - 2 a.b with a, b in {0,1}^512 held as bytes; QT query tiles of 16 per wave, so every
+// train fragment read from LDS feeds QT MFMAs.
 typedef int v4i __attribute__((ext_vector_type(4)));
 // Row stride of a staged train tile: 512 + 32 bytes.  A ds_read_b128 is served in four groups of 16 lanes --
 // {0-3,12-15,20-27}, {4-11,16-19,28-31} and the same + 32 (MI355X_MICROARCH.md, LDS) -- i.e. rows of two neighbouring
@@ -1008,132 +1007,7 @@ __device__ __forceinline__ void top2_push(uint32_t &b0, uint32_t &b1, uint32_t k
     b0 = min(b0, k);
 }
 
-// QT query tiles of 16 per wave: every train fragment read from LDS feeds QT MFMAs
-template <int QT, int NW>
-__global__ __launch_bounds__(64 * NW) void k_ov_match(const int8_t *__restrict__ qbits, const int32_t *__restrict__ qpop,
-                                                 const int32_t *__restrict__ qn, const int8_t *__restrict__ tbits,
-                                                 const int32_t *__restrict__ tpop, const int32_t *__restrict__ tn,
-                                                 const int32_t *__restrict__ pair_q, const int32_t *__restrict__ pair_t,
-                                                 int32_t *__restrict__ out_idx /*[P][MAXKP][2]*/, int32_t *__restrict__ out_dist)
-{
-    extern __shared__ __attribute__((aligned(16))) int8_t s_t[];      // [64][MT_ROW]
-    const int p = blockIdx.y;
-    const int fq = pair_q[p], ft = pair_t[p];
-    const int nq = qn[fq], nt = tn[ft];
-    const int q0 = blockIdx.x * (16 * NW * QT);
-    if (q0 >= nq) return;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int row = lane & 15, kb = lane >> 4;
-    const int8_t *Q = qbits + (size_t)fq * MAXKP * DESC_K;
-    const int8_t *T = tbits + (size_t)ft * MAXKP * DESC_K;
-    // A fragments: query (q0 + (wave * QT + u) * 16 + row), bytes [64*ks + 16*kb, +16)
-    v4i a[QT][8];
-    int cq[QT][4];                   // popcount of this lane's 4 accumulator rows
-    uint32_t b0[QT][4], b1[QT][4];
-#pragma unroll
-    for (int u = 0; u < QT; ++u) {
-        const int qrow = q0 + (wave * QT + u) * 16 + row;
-#pragma unroll
-        for (int ks = 0; ks < 8; ++ks)
-            a[u][ks] = *reinterpret_cast<const v4i *>(Q + (size_t)qrow * DESC_K + ks * 64 + kb * 16);
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            cq[u][r] = qpop[(size_t)fq * MAXKP + q0 + (wave * QT + u) * 16 + kb * 4 + r];
-            b0[u][r] = b1[u][r] = MT_EMPTY;
-        }
-    }
-    // 64 train descriptors (32 KB) per tile: 2048 16-byte pieces, 8 per thread.  The NEXT tile's pieces are requested
-    // into registers before this tile's MFMAs, so the global-memory latency (it was exposed twice per tile between the
-    // barriers and held the kernel at 18 % of the matrix peak) hides behind them.
-    constexpr int NP = 2048 / (64 * NW);      // 16-byte pieces per thread
-    v4i stage[NP];
-    auto fetch = [&](int t0) {
-#pragma unroll
-        for (int j = 0; j < NP; ++j) {
-            const int i = threadIdx.x + 64 * NW * j, tr = i >> 5, piece = i & 31;
-            stage[j] = *reinterpret_cast<const v4i *>(T + (size_t)(t0 + tr) * DESC_K + piece * 16);
-        }
-    };
-    // two LDS tiles: while tile t is multiplied, the registers holding tile t+1 (requested a whole tile earlier) are
-    // parked in the other buffer and tile t+2 is requested -- ONE barrier per tile, no wait on global memory in the loop
-    auto park = [&](int8_t *buf) {
-#pragma unroll
-        for (int j = 0; j < NP; ++j) {
-            const int i = threadIdx.x + 64 * NW * j, tr = i >> 5, piece = i & 31;
-            *reinterpret_cast<v4i *>(buf + (size_t)tr * MT_ROW + piece * 16) = stage[j];
-        }
-    };
-    int8_t *const bufA = s_t, *const bufB = s_t + (size_t)64 * MT_ROW;
-    if (nt > 0) {
-        fetch(0);
-        park(bufA);
-        if (64 < nt) fetch(64);                  // rows up to MAXKP exist for every slot (zero descriptors past the count)
-    }
-    __syncthreads();
-    for (int t0 = 0, it = 0; t0 < nt; t0 += 64, ++it) {
-        const int8_t *cur = (it & 1) ? bufB : bufA;
-        // (|b| + 512) << 11 | t for this lane's four train columns of the tile (a dead column, t >= nt, keeps every key
-        // above any live key); requested before the MFMAs so that the popcount loads hide behind them.  The query's own
-        // popcount is the same for all candidates of a row, so it is added when the result is written, not per candidate.
-        // A dead column's key must not depend on what its descriptor row holds (k_ov_describe and uwip_features_upload
-        // zero the rows past the count, but nothing else guarantees it): its dot product is multiplied by 0 instead of
-        // -4096, at no cost in the epilogue (the multiplier of the v_mad_i32_i24 is a register either way).
-        uint32_t tb[4];
-        int mf[4];
-#pragma unroll
-        for (int tt = 0; tt < 4; ++tt) {
-            const int t = t0 + tt * 16 + row;
-            tb[tt] = t < nt ? ((((uint32_t)tpop[(size_t)ft * MAXKP + t] + 512u) << 11) | (uint32_t)t) : 0x7ff00000u;
-            mf[tt] = t < nt ? -4096 : 0;
-        }
-#pragma unroll
-        for (int tt = 0; tt < 4; ++tt) {
-            v4i acc[QT];
-#pragma unroll
-            for (int u = 0; u < QT; ++u) acc[u] = v4i{0, 0, 0, 0};
-#pragma unroll
-            for (int ks = 0; ks < 8; ++ks) {
-                const v4i b = *reinterpret_cast<const v4i *>(cur + (size_t)(tt * 16 + row) * MT_ROW + ks * 64 + kb * 16);
-#pragma unroll
-                for (int u = 0; u < QT; ++u) acc[u] = __builtin_amdgcn_mfma_i32_16x16x64_i8(a[u][ks], b, acc[u], 0, 0, 0);
-            }
-            // C/D: col = lane & 15 (train t), row = (lane >> 4) * 4 + reg (query).  popcount(a xor b) = |a| + |b| - 2 a.b:
-            // key = tb - (a.b << 12), one v_mad_i32_i24
-#pragma unroll
-            for (int u = 0; u < QT; ++u)
-#pragma unroll
-                for (int r = 0; r < 4; ++r)
-                    top2_push(b0[u][r], b1[u][r], (uint32_t)(__mul24(acc[u][r], mf[tt]) + (int)tb[tt]));
-        }
-        if (t0 + 64 < nt) {
-            park((it & 1) ? bufA : bufB);        // tile t+1: its buffer was last read in iteration t-1, before that barrier
-            if (t0 + 128 < nt) fetch(t0 + 128);
-        }
-        __syncthreads();
-    }
-    // merge the 16 lanes (lane & 15) that hold different columns of the same query rows
-#pragma unroll
-    for (int u = 0; u < QT; ++u)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-#pragma unroll
-            for (int d = 1; d < 16; d <<= 1) {
-                const uint32_t o0 = (uint32_t)__shfl_xor((int)b0[u][r], d, 64), o1 = (uint32_t)__shfl_xor((int)b1[u][r], d, 64);
-                top2_push(b0[u][r], b1[u][r], o0);
-                top2_push(b0[u][r], b1[u][r], o1);
-            }
-            const int q = q0 + (wave * QT + u) * 16 + kb * 4 + r;
-            if (row == 0 && q < nq) {
-                const size_t o = ((size_t)p * MAXKP + q) * 2;
-                const bool h0 = b0[u][r] < 0x7ff00000u, h1 = b1[u][r] < 0x7ff00000u;
-                out_idx[o] = h0 ? (int)(b0[u][r] & 2047u) : -1; out_idx[o + 1] = h1 ? (int)(b1[u][r] & 2047u) : -1;
-                out_dist[o] = h0 ? (int)(b0[u][r] >> 11) - 512 + cq[u][r] : -1;
-                out_dist[o + 1] = h1 ? (int)(b1[u][r] >> 11) - 512 + cq[u][r] : -1;
-            }
-        }
-}
-
-// The same matcher, software-pipelined (round 4).  What the ISA of the form above shows (llvm-objdump): (i) the four
+// Software-pipelined (round 4).  What the ISA of the plain form of rounds 2-3 showed (llvm-objdump): (i) the four
 // `tpop` loads of a tile sit behind four lane-mask branches, each followed by `s_waitcnt vmcnt(0)` -- four serialised
 // global-memory round trips per 64 MFMAs; (ii) the whole top-2 epilogue of a tile (112 vector instructions) runs AFTER its
 // 64 MFMAs, right before the barrier, so all eight waves of the block alternate between a matrix phase and a vector
@@ -1145,7 +1019,7 @@ __global__ __launch_bounds__(64 * NW) void k_ov_match(const int8_t *__restrict__
 //     -- an MFMA holds the SIMD's vector issue for 8 of its 16 cycles, two vector instructions fit in the rest
 //     (MI355X_MICROARCH.md, "vector-instruction ISSUE cost") -- pinned with sched_group_barrier.
 // Same results bit for bit (packed-key top-2 is order-independent).
-template <int QT, int NW, int TG>      // TG: column groups of 16 per staged train tile (4 or 8): one barrier per TG * 16 columns
+template <int QT, int NW, int TG>      // TG: column groups of 16 per staged train tile: one barrier per TG * 16 columns
 __global__ __launch_bounds__(64 * NW) void k_ov_match_sp(const int8_t *__restrict__ qbits, const int32_t *__restrict__ qpop,
                                                     const int32_t *__restrict__ qn, const int8_t *__restrict__ tbits,
                                                     const int32_t *__restrict__ tpop, const int32_t *__restrict__ tn,
@@ -2395,7 +2269,7 @@ UWIP_API int uwip_overlap_match_ex(uwip_ctx *ctx, const uwip_features *fq, const
     {
         uwip_kscope ks(ctx, "k_ov_match");
         constexpr int QT = 2;            // 2 query tiles of 16 per wave
-        // UWIP_MATCH_FORM: 4 (default) FP4 operands; 3 the i8 form of round 4; 0 / 2 / 5 / 6 older and experimental shapes
+        // UWIP_MATCH_FORM: 4 (default) FP4 operands; 3 the i8 form of round 4; 5 / 6 experimental FP4 shapes
         auto read_form = [] { const char *e = std::getenv("UWIP_MATCH_FORM"); return e && *e ? std::atoi(e) : 4; };
         static const int form_once = read_form();
         const int form = uwip_test_hooks() ? read_form() : form_once;      // tests switch forms inside one process
@@ -2406,7 +2280,7 @@ UWIP_API int uwip_overlap_match_ex(uwip_ctx *ctx, const uwip_features *fq, const
             KERNEL<<<dim3(MAXKP / (16 * (NWV) * QT), npairs), 64 * (NWV), (LDSB), ctx->stream>>>(fq->d_bits, fq->d_pop, fq->d_n, ft->d_bits, \
                                                                                          ft->d_pop, ft->d_n, d_pairs, d_pairs + npairs, m_idx, m_dist); \
         } while (0)
-        const size_t lds0 = (size_t)2 * 64 * MT_ROW, lds1 = lds0 + 2 * 64 * sizeof(uint32_t), lds2 = 2 * lds1;
+        const size_t ldsi8 = (size_t)2 * 64 * MT_ROW + 2 * 64 * sizeof(uint32_t);
 #define UWIP_LAUNCH_MATCH_F4(KERNEL, NWV, LDSB)                                                                                \
         do {                                                                                                                   \
             int rc_l = uwip_lds_optin(ctx, #KERNEL, (const void *)KERNEL, (LDSB));                                             \
@@ -2415,10 +2289,8 @@ UWIP_API int uwip_overlap_match_ex(uwip_ctx *ctx, const uwip_features *fq, const
                                                                                          ft->d_pop, ft->d_n, d_pairs, d_pairs + npairs, m_idx, m_dist); \
         } while (0)
         const size_t ldsf4 = (size_t)2 * 64 * F4_ROW + 2 * 64 * sizeof(float), ldsf8 = (size_t)2 * 128 * F4_ROW + 2 * 128 * sizeof(float);
-        switch (form) {                  // variants kept for A/B (tools/matcher_only.py): 0 = the round 2-3 kernel
-        case 0: UWIP_LAUNCH_MATCH((k_ov_match<QT, 8>), 8, lds0); break;
-        case 2: UWIP_LAUNCH_MATCH((k_ov_match_sp<QT, 8, 8>), 8, lds2); break;       // 128 train columns per barrier
-        case 3: UWIP_LAUNCH_MATCH((k_ov_match_sp<QT, 8, 4>), 8, lds1); break;       // round 4's i8 form
+        switch (form) {                  // unknown values run the default
+        case 3: UWIP_LAUNCH_MATCH((k_ov_match_sp<QT, 8, 4>), 8, ldsi8); break;      // round 4's i8 form
         case 5: UWIP_LAUNCH_MATCH_F4((k_ov_match_f4<QT, 8, 8>), 8, ldsf8); break;   // FP4, 128 train columns per barrier
         case 6: UWIP_LAUNCH_MATCH_F4((k_ov_match_f4<QT, 4, 4>), 4, ldsf4); break;   // FP4, 4-wave blocks
         default: UWIP_LAUNCH_MATCH_F4((k_ov_match_f4<QT, 8, 4>), 8, ldsf4); break;  // FP4 operands (round 5)
