@@ -4,8 +4,13 @@
 //   calcOverlap of every frame against its predecessor (modules/videostrip/src/videostrip.cpp:192-289)
 // on the frames of a Motion-JPEG .avi or of a frame list, in batches through page-locked host buffers
 // (uwip_pipe_step_host: batch k + 1 is uploaded and batch k - 1 leaves while batch k's kernels run).
-//   uwpipe [-b N] [-c LETTERS] [-w N] [--guard-s] [--min6] [--relative-threshold] [--png] <video.avi | frame_list.txt> <output_prefix>
+//   uwpipe [-b N] [-c LETTERS] [-w N] [--guard-s] [--min6] [--relative-threshold] [--png]
+//          [--keyframes [-k N] [-p X] [--lookback D]] <video.avi | frame_list.txt> <output_prefix>
 // writes <prefix>NNNN.jpg (the enhanced frames) and <prefix>uwpipe_report.txt (TSV: ID, Filename, Overlap, BS, CL).
+// --keyframes: the overlap stage runs videostrip's key-frame selector (main.cpp:284-394) on the enhanced frames, on the
+// device (uwip_pipe_keyframe_chain); <prefix>videostrip_report.txt gets its rows with the reference's columns (ID, Frame,
+// Filename, Overlap, Blur), Filename = the enhanced frame that is the key frame.  Overlap in uwpipe_report.txt is then the
+// overlap against the current key frame (nan: not compared).
 // Defaults are the reference's rules (uwip_pipe_config_default); the three switches are the library's opt-in deviations.
 #include <algorithm>
 #include <cstring>
@@ -15,14 +20,19 @@
 
 int main(int argc, char **argv)
 {
-    const Args a = parse_args(argc, argv, {"b", "batch", "c", "w", "window"});
+    const Args a = parse_args(argc, argv, {"b", "batch", "c", "w", "window", "k", "p", "lookback"});
     if (a.pos.size() < 2 || a.has("h") || a.has("help")) {
         std::printf("uwpipe - bgdehaze -> histretch -> aclahe -> overlap of every frame against its predecessor\n"
-                    "usage: uwpipe [-b N] [-c LETTERS] [-w N] [--guard-s] [--min6] [--relative-threshold] [--png] <video.avi (Motion-JPEG) | frame_list.txt> <output_prefix>\n"
+                    "usage: uwpipe [-b N] [-c LETTERS] [-w N] [--guard-s] [--min6] [--relative-threshold] [--png]\n"
+                    "              [--keyframes [-k N] [-p X] [--lookback D]] <video.avi (Motion-JPEG) | frame_list.txt> <output_prefix>\n"
                     "  -b N      frames per step (default 8)\n"
                     "  -c L      histretch letters (default RGB)\n"
                     "  -w N      bgdehaze window (default 15)\n"
-                    "  --guard-s / --min6 / --relative-threshold   the library's opt-in deviations from the reference's rules (uwip.h)\n");
+                    "  --guard-s / --min6 / --relative-threshold   the library's opt-in deviations from the reference's rules (uwip.h)\n"
+                    "  --keyframes   select key frames as videostrip does (report: <prefix>videostrip_report.txt)\n"
+                    "  -k N          frames of the refinement window (default 11)\n"
+                    "  -p X          minOverlap (default 0.4)\n"
+                    "  --lookback D  frames matched ahead per frame (a speed knob; the results do not depend on it)\n");
         return 0;
     }
     const std::string InputFile = a.pos[0], OutputFile = a.pos[1];
@@ -61,6 +71,23 @@ int main(int argc, char **argv)
         if (a.has("min6")) cfg.match_flags |= UWIP_OVERLAP_MIN6;
         if (a.has("relative-threshold")) cfg.detect_flags |= UWIP_OVERLAP_RELATIVE_THRESHOLD;
         CK(uwip_pipe_create(ctx, &cfg, nullptr, &pipe), "uwip_pipe_create");
+        const bool kf = a.has("keyframes");
+        uwip_keyframe_config kc;
+        uwip_keyframe_config_default(&kc);
+        if (a.has("k")) kc.kWindow = std::atoi(a.get("k", "11").c_str());
+        if (a.has("p")) kc.minOverlap = (float)std::atof(a.get("p", "0.4").c_str());
+        if (a.has("lookback")) kc.lookback = std::atoi(a.get("lookback", "8").c_str());
+        if (kf) CK(uwip_pipe_keyframe_chain(pipe, &kc), "uwip_pipe_keyframe_chain");
+        std::ofstream kreport;
+        std::vector<uwip_keyframe_row> krows(256);
+        const size_t kread = (size_t)std::max(1, kc.max_rows / (2 * (B + 1)));
+        if (kf) {
+            kreport.open(OutputFile + "videostrip_report.txt");
+            kreport << "Input:\t" << InputFile << "\n";
+            kreport << "Video metadata:\n\tSize:\t" << cols << " x " << rows << "\n\tFrames:\t" << n << "\n\thResize:\t"
+                    << (float)640 / (float)cols << "\nTarget minOverlap:\t" << kc.minOverlap << "\nWindow size:\t" << kc.kWindow << "\n";
+            kreport << "***************************************\nID\tFrame\tFilename\tOverlap\tBlur\n";
+        }
         for (int s = 0; s < 2; ++s) CK(uwip_host_alloc(ctx, fbytes * B, &h_in[s]), "uwip_host_alloc");
         CK(uwip_host_alloc(ctx, fbytes * B, &h_out), "uwip_host_alloc");
         CK(uwip_host_alloc(ctx, sizeof(float) * B, &h_ratio), "uwip_host_alloc");
@@ -91,6 +118,7 @@ int main(int argc, char **argv)
                 CK(uwip_pipe_wait(pipe, prev_up), "uwip_pipe_wait");           // h_in[(k + 1) & 1] has left for the device
                 if (!fill(k + 1, h_in[(k + 1) & 1])) { rc = UWIP_ERR_INVALID; what = "reading the input"; goto fail; }
             }
+            if (kf && !more) CK(uwip_pipe_end_of_stream(pipe, (int)(n - k * B)), "uwip_pipe_end_of_stream");   // the padding stays out
             uint64_t t[3];
             CK(uwip_pipe_step_host(pipe, h_in[k & 1], h_out, (float *)h_ratio, more ? h_in[(k + 1) & 1] : nullptr, t), "uwip_pipe_step_host");
             prev_up = t[0];
@@ -107,6 +135,19 @@ int main(int argc, char **argv)
                 if (!imgio::imwrite(name, out)) { std::printf("cannot write %s\n", name); rc = UWIP_ERR_INVALID; what = "writing"; goto fail; }
                 // frame 0 is its own key frame (main.cpp:284-297): its row carries the self-overlap
                 report << i << "\t" << name << "\t" << ((float *)h_ratio)[j] << "\t" << bs[j] << "\t" << cl[j] << "\n";
+            }
+            // the rows are read every `kread` batches and after the last one (each read drains the stream): at most B + 1 rows
+            // close per batch, so the ring (max_rows) never holds more than half of its capacity unread
+            const bool read_rows = kf && ((k + 1) % kread == 0 || !more);
+            for (int got = (int)krows.size(); read_rows && got == (int)krows.size();) {
+                CK(uwip_pipe_keyframes(pipe, krows.data(), (int)krows.size(), &got), "uwip_pipe_keyframes");
+                for (int r = 0; r < got; ++r) {
+                    const uwip_keyframe_row &w = krows[r];
+                    char name[512];
+                    std::snprintf(name, sizeof name, "%s%04d.%s", OutputFile.c_str(), w.index, ext);
+                    if (w.id == 0) kreport << "0\t0\t" << name << "\t0.0\t0.0\n";              // main.cpp:297
+                    else kreport << w.id << "\t" << w.frame << "\t" << name << "\t" << w.overlap << "\t" << w.blur << "\n";   // :381
+                }
             }
             std::printf("\rbatch %zu / %zu", k + 1, nb);
             std::fflush(stdout);

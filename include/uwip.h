@@ -528,6 +528,60 @@ int uwip_pipe_last_params(uwip_pipe *p, int32_t *h_bs, int32_t *h_cl);
 int uwip_pipe_device_results(uwip_pipe *p, const uint8_t **d_v, const uint8_t **d_frames, const float **d_ratio,
                              const int32_t **d_info);
 
+/* ---- key-frame mode: videostrip's selector on the enhanced frames ---------------------------------------------------
+ * Opt-in per pipe (uwip_pipe_keyframe_chain); without it the overlap stage compares every frame with its predecessor, as
+ * above.  In key-frame mode the overlap stage runs main.cpp:284-394 over the stream of frames it is given, across steps:
+ * stream frame 0 is the first key frame (row (0, 0, 0.0, 0.0)); every later frame outside a refinement window gets
+ * calcOverlap(key, frame); -2.0 counts as OVERLAP_MIN + 0.01 = 0.41 (:321-329); a result <= minOverlap opens a window: the
+ * trigger and the next kWindow frames are candidates by calcBlur(resize(frame)) alone, a later one replaces the best only
+ * when its blur is strictly greater, and the best becomes the new key frame (:335-381).  "Frame" keeps the reference's
+ * numbering: a trigger that stays best reports its 0-based stream index (:340), a window frame the 1-based count of frames
+ * read (:364).  When the stream ends inside a window the row is written with the best candidate so far.
+ * Every decision is made on the device, behind the matcher: the step never waits on the host (key-frame mode).
+ * d_ratio[i] is frame i's raw calcOverlap against the key it was compared with (-2.0: no homography; NaN: not compared --
+ * a window frame, stream frame 0, a frame past `valid`); d_info[i][0..4] as uwip_overlap_match for that pair, d_info[i][5]
+ * the key's stream index (-1: not compared).  The host form's h_ratio follows the same rule. */
+typedef struct uwip_keyframe_config {
+    float   minOverlap;   /* -p, default 0.4 (videostrip.hpp:50) */
+    int32_t kWindow;      /* -k, default 11 (videostrip.hpp:51); 0 = no refinement */
+    int32_t lookback;     /* D >= 1: frames i - 1..i - D of the batch are matched against frame i ahead of the decisions;
+                             a pure performance knob, the results are identical for every D */
+    int32_t max_rows;     /* capacity of the pipe's row ring (>= 1), default 4096 */
+} uwip_keyframe_config;
+typedef struct uwip_keyframe_row {      /* 32 bytes */
+    int32_t id, frame;                  /* report ID and "Frame" (main.cpp:381) */
+    int32_t index;                      /* 0-based stream index of the key frame: which enhanced frame to write */
+    float   overlap, blur;              /* trigger overlap (after -2.0 -> 0.41), best blur (0, 0 in row 0) */
+    int32_t reserved[3];
+} uwip_keyframe_row;
+int uwip_keyframe_config_default(uwip_keyframe_config *kc);          /* 0.4, 11, lookback 8, 4096 rows */
+/* Switch the pipe to key-frame mode (or re-configure it): before the first step or right after uwip_pipe_reset.  Waits for
+ * the stream (it re-allocates the feature slots and uploads the fixed pair list). */
+int uwip_pipe_keyframe_chain(uwip_pipe *p, const uwip_keyframe_config *kc);
+/* The NEXT step that runs the overlap stage is the stream's last, and only its first `valid` frames (1..frames) are real (a
+ * caller that pads its last batch by repeating a frame passes the real count).  In key-frame mode only those frames enter
+ * the chain: the padding is not compared (NaN ratios) and a window still open is closed with its best so far.  In the
+ * predecessor mode `valid` changes nothing in that step: every frame, padding included, is matched against its predecessor
+ * as before.  In both modes the pipe starts a new stream after that step, as after a reset. */
+int uwip_pipe_end_of_stream(uwip_pipe *p, int valid);
+/* Rows closed since the last call, up to `cap` of them (*n = how many; call again while *n == cap).  Waits for the stream.
+ * An error when the caller fell more than max_rows rows behind (those rows are gone: the call says so instead of dropping
+ * them silently) or when a batch was not resolved within the round bound (reported once; the chain then stays stopped until
+ * the next stream begins). */
+int uwip_pipe_keyframes(uwip_pipe *p, uwip_keyframe_row *h_rows, int cap, int *n);
+/* The same decision chain with the same batch / round scheme on the host, the overlaps and blurs coming from callbacks:
+ * overlap(user, key, frame) = calcOverlap of stream frame `frame` against stream frame `key`, blur(user, frame) =
+ * calcBlur(resize(frame)).  n_frames frames in batches of `batch`, the last one holding the rest (end of stream).  Writes up
+ * to `cap` rows (*n_rows = all rows) and, when `rounds` != NULL, the fallback rounds each batch used ([ceil(n_frames /
+ * batch)]).  No device needed: the tests check the device chain's logic against the reference loop with it. */
+typedef float (*uwip_kf_overlap_fn)(void *user, int32_t key, int32_t frame);
+typedef float (*uwip_kf_blur_fn)(void *user, int32_t frame);
+int uwip_keyframe_chain_host(const uwip_keyframe_config *kc, int n_frames, int batch, uwip_kf_overlap_fn overlap,
+                             uwip_kf_blur_fn blur, void *user, uwip_keyframe_row *rows, int cap, int *n_rows, int32_t *rounds);
+/* The fallback-round bound R a pipe queues per step (key-frame mode): (frames - 1) / s + 1 with s = kWindow + 1,
+ * or s = min(lookback, frames - 1) + 1 when kWindow = 0.  -1 for a bad configuration. */
+int uwip_keyframe_max_rounds(const uwip_keyframe_config *kc, int frames);
+
 #ifdef __cplusplus
 }
 #endif

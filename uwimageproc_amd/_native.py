@@ -59,6 +59,23 @@ class PipeConfig(C.Structure):
     ]
 
 
+class KeyframeConfig(C.Structure):
+    """Mirror of ``uwip_keyframe_config``."""
+
+    _fields_ = [("minOverlap", C.c_float), ("kWindow", C.c_int32), ("lookback", C.c_int32), ("max_rows", C.c_int32)]
+
+
+class KeyframeRow(C.Structure):
+    """Mirror of ``uwip_keyframe_row`` (32 bytes)."""
+
+    _fields_ = [("id", C.c_int32), ("frame", C.c_int32), ("index", C.c_int32), ("overlap", C.c_float), ("blur", C.c_float),
+                ("reserved", C.c_int32 * 3)]
+
+
+# uwip_keyframe_chain_host's callbacks
+KF_OVERLAP_FN = C.CFUNCTYPE(C.c_float, C.c_void_p, C.c_int32, C.c_int32)
+KF_BLUR_FN = C.CFUNCTYPE(C.c_float, C.c_void_p, C.c_int32)
+
 _lib: Optional[C.CDLL] = None
 
 # name -> (restype, argtypes); every symbol include/uwip.h declares
@@ -151,6 +168,13 @@ SIGNATURES = {
     "uwip_pipe_reset": (C.c_int, [_P]),
     "uwip_pipe_last_params": (C.c_int, [_P, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "uwip_pipe_device_results": (C.c_int, [_P, C.POINTER(_P), C.POINTER(_P), C.POINTER(_P), C.POINTER(_P)]),
+    "uwip_keyframe_config_default": (C.c_int, [C.POINTER(KeyframeConfig)]),
+    "uwip_keyframe_max_rounds": (C.c_int, [C.POINTER(KeyframeConfig), C.c_int]),
+    "uwip_pipe_keyframe_chain": (C.c_int, [_P, C.POINTER(KeyframeConfig)]),
+    "uwip_pipe_end_of_stream": (C.c_int, [_P, C.c_int]),
+    "uwip_pipe_keyframes": (C.c_int, [_P, C.POINTER(KeyframeRow), C.c_int, C.POINTER(C.c_int)]),
+    "uwip_keyframe_chain_host": (C.c_int, [C.POINTER(KeyframeConfig), C.c_int, C.c_int, KF_OVERLAP_FN, KF_BLUR_FN, _P,
+                                           C.POINTER(KeyframeRow), C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int32)]),
 }
 
 

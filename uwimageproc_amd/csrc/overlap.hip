@@ -1024,10 +1024,12 @@ __global__ __launch_bounds__(64 * NW) void k_ov_match_sp(const int8_t *__restric
                                                     const int32_t *__restrict__ qn, const int8_t *__restrict__ tbits,
                                                     const int32_t *__restrict__ tpop, const int32_t *__restrict__ tn,
                                                     const int32_t *__restrict__ pair_q, const int32_t *__restrict__ pair_t,
-                                                    int32_t *__restrict__ out_idx /*[P][MAXKP][2]*/, int32_t *__restrict__ out_dist)
+                                                    int32_t *__restrict__ out_idx /*[P][MAXKP][2]*/, int32_t *__restrict__ out_dist,
+                                                    const int32_t *__restrict__ d_npairs /*null: every launched pair*/)
 {
     extern __shared__ __attribute__((aligned(16))) int8_t s_t[];      // 2 x [64][MT_ROW] descriptors, then 2 x [64] keys
     const int p = blockIdx.y;
+    if (d_npairs && p >= *d_npairs) return;
     const int fq = pair_q[p], ft = pair_t[p];
     const int nq = qn[fq], nt = tn[ft];
     const int q0 = blockIdx.x * (16 * NW * QT);
@@ -1204,10 +1206,12 @@ __global__ __launch_bounds__(64 * NW) void k_ov_match_f4(const uint32_t *__restr
                                                     const int32_t *__restrict__ qn, const uint32_t *__restrict__ tnib,
                                                     const int32_t *__restrict__ tpop, const int32_t *__restrict__ tn,
                                                     const int32_t *__restrict__ pair_q, const int32_t *__restrict__ pair_t,
-                                                    int32_t *__restrict__ out_idx /*[P][MAXKP][2]*/, int32_t *__restrict__ out_dist)
+                                                    int32_t *__restrict__ out_idx /*[P][MAXKP][2]*/, int32_t *__restrict__ out_dist,
+                                                    const int32_t *__restrict__ d_npairs /*null: every launched pair*/)
 {
     extern __shared__ __attribute__((aligned(16))) int8_t s_t[];      // 2 x [TC][F4_ROW] descriptors, then 2 x [TC] keys
     const int p = blockIdx.y;
+    if (d_npairs && p >= *d_npairs) return;
     const int fq = pair_q[p], ft = pair_t[p];
     const int nq = qn[fq], nt = tn[ft];
     const int q0 = blockIdx.x * (16 * NW * QT);
@@ -1590,7 +1594,8 @@ __global__ __launch_bounds__(256) void k_ov_geometry(const Keypoint *__restrict_
                                                     const int32_t *__restrict__ m_idx, const int32_t *__restrict__ m_dist,
                                                     int w, int h, int videoW, int videoH, uint32_t seed, int min_inliers,
                                                     float *__restrict__ ratio, int32_t *__restrict__ info /*[P][8]*/,
-                                                    double *__restrict__ Hout /*[P][9]*/)
+                                                    double *__restrict__ Hout /*[P][9]*/,
+                                                    const int32_t *__restrict__ d_npairs /*null: every launched pair*/)
 {
     extern __shared__ __attribute__((aligned(16))) uint8_t s_raw[];
     // carve: good points 4 x MAXKP floats (32 KB) | inlier flags MAXKP (2 KB) | mask (38.4 KB) | spans (1.9 KB)
@@ -1605,6 +1610,7 @@ __global__ __launch_bounds__(256) void k_ov_geometry(const Keypoint *__restrict_
     __shared__ int s_ng;
 
     const int p = blockIdx.x, tid = threadIdx.x;
+    if (d_npairs && p >= *d_npairs) return;
     const int fq = pair_q[p], ft = pair_t[p];
     const int nq = qn[fq], nt = tn[ft];
     const Keypoint *KQ = qkp + (size_t)fq * MAXKP, *KT = tkp + (size_t)ft * MAXKP;
@@ -2219,6 +2225,58 @@ UWIP_API int uwip_overlap_debug_level(uwip_ctx *ctx, int frame, int level, int r
     return UWIP_OK;
 }
 
+// The matcher and the geometry on pair lists already in device memory: d_pq / d_pt [npairs] slot indices.  d_npairs
+// (null: all npairs) is a count the device itself wrote: the launches cover npairs pairs, the blocks at or beyond the count
+// return at once (the key-frame chain's fallback rounds, kf_chain.hpp).
+static int launch_match(uwip_ctx *ctx, const uwip_features *fq, const uwip_features *ft, const int32_t *d_pq, const int32_t *d_pt,
+                        const int32_t *d_npairs, int npairs, int videoWidth, int videoHeight, uint32_t seed, int min_inliers,
+                        float *d_ratio, int32_t *info, double *d_H, int32_t *m_idx, int32_t *m_dist)
+{
+    {
+        uwip_kscope ks(ctx, "k_ov_match");
+        constexpr int QT = 2;            // 2 query tiles of 16 per wave
+        // UWIP_MATCH_FORM: 4 (default) FP4 operands; 3 the i8 form of round 4; 5 / 6 experimental FP4 shapes
+        auto read_form = [] { const char *e = std::getenv("UWIP_MATCH_FORM"); return e && *e ? std::atoi(e) : 4; };
+        static const int form_once = read_form();
+        const int form = uwip_test_hooks() ? read_form() : form_once;      // tests switch forms inside one process
+#define UWIP_LAUNCH_MATCH(KERNEL, NWV, LDSB)                                                                                   \
+        do {                                                                                                                   \
+            int rc_l = uwip_lds_optin(ctx, #KERNEL, (const void *)KERNEL, (LDSB));                                             \
+            if (rc_l) return rc_l;                                                                                             \
+            KERNEL<<<dim3(MAXKP / (16 * (NWV) * QT), npairs), 64 * (NWV), (LDSB), ctx->stream>>>(fq->d_bits, fq->d_pop, fq->d_n, ft->d_bits, \
+                                                                                         ft->d_pop, ft->d_n, d_pq, d_pt, m_idx, m_dist, d_npairs); \
+        } while (0)
+        const size_t ldsi8 = (size_t)2 * 64 * MT_ROW + 2 * 64 * sizeof(uint32_t);
+#define UWIP_LAUNCH_MATCH_F4(KERNEL, NWV, LDSB)                                                                                \
+        do {                                                                                                                   \
+            int rc_l = uwip_lds_optin(ctx, #KERNEL, (const void *)KERNEL, (LDSB));                                             \
+            if (rc_l) return rc_l;                                                                                             \
+            KERNEL<<<dim3(MAXKP / (16 * (NWV) * QT), npairs), 64 * (NWV), (LDSB), ctx->stream>>>(fq->d_nib, fq->d_pop, fq->d_n, ft->d_nib, \
+                                                                                         ft->d_pop, ft->d_n, d_pq, d_pt, m_idx, m_dist, d_npairs); \
+        } while (0)
+        const size_t ldsf4 = (size_t)2 * 64 * F4_ROW + 2 * 64 * sizeof(float), ldsf8 = (size_t)2 * 128 * F4_ROW + 2 * 128 * sizeof(float);
+        switch (form) {                  // unknown values run the default
+        case 3: UWIP_LAUNCH_MATCH((k_ov_match_sp<QT, 8, 4>), 8, ldsi8); break;      // round 4's i8 form
+        case 5: UWIP_LAUNCH_MATCH_F4((k_ov_match_f4<QT, 8, 8>), 8, ldsf8); break;   // FP4, 128 train columns per barrier
+        case 6: UWIP_LAUNCH_MATCH_F4((k_ov_match_f4<QT, 4, 4>), 4, ldsf4); break;   // FP4, 4-wave blocks
+        default: UWIP_LAUNCH_MATCH_F4((k_ov_match_f4<QT, 8, 4>), 8, ldsf4); break;  // FP4 operands (round 5)
+        }
+#undef UWIP_LAUNCH_MATCH_F4
+#undef UWIP_LAUNCH_MATCH
+        UWIP_HIP(ctx, hipGetLastError());
+    }
+    {
+        uwip_kscope ks(ctx, "k_ov_geometry");
+        const size_t lds = (size_t)MAXKP * 16 + MAXKP + (size_t)TH * MASK_WORDS * 4 + (size_t)TH * 4;
+        int rc = uwip_lds_optin(ctx, "k_ov_geometry", (const void *)k_ov_geometry, lds);
+        if (rc) return rc;
+        k_ov_geometry<<<npairs, 256, lds, ctx->stream>>>(fq->d_kp, ft->d_kp, fq->d_n, ft->d_n, d_pq, d_pt, m_idx, m_dist,
+                                                        fq->w, fq->h, videoWidth, videoHeight, seed, min_inliers, d_ratio, info, d_H, d_npairs);
+        UWIP_HIP(ctx, hipGetLastError());
+    }
+    return UWIP_OK;
+}
+
 // match query slots against train slots and turn each pair into an overlap ratio.
 // h_pair_q / h_pair_t: host arrays of slot indices (query = object frame, train = key frame).
 // d_ratio [npairs]: overlap ratio or -2.0 (videostrip.cpp:252-256,272).  d_info (may be NULL) [npairs][8]:
@@ -2266,49 +2324,8 @@ UWIP_API int uwip_overlap_match_ex(uwip_ctx *ctx, const uwip_features *fq, const
         ctx->ov_pairs_host.assign(h_pairs, h_pairs + 2 * (size_t)npairs);
         ctx->ov_pairs_dev = d_pairs;
     }
-    {
-        uwip_kscope ks(ctx, "k_ov_match");
-        constexpr int QT = 2;            // 2 query tiles of 16 per wave
-        // UWIP_MATCH_FORM: 4 (default) FP4 operands; 3 the i8 form of round 4; 5 / 6 experimental FP4 shapes
-        auto read_form = [] { const char *e = std::getenv("UWIP_MATCH_FORM"); return e && *e ? std::atoi(e) : 4; };
-        static const int form_once = read_form();
-        const int form = uwip_test_hooks() ? read_form() : form_once;      // tests switch forms inside one process
-#define UWIP_LAUNCH_MATCH(KERNEL, NWV, LDSB)                                                                                   \
-        do {                                                                                                                   \
-            int rc_l = uwip_lds_optin(ctx, #KERNEL, (const void *)KERNEL, (LDSB));                                             \
-            if (rc_l) return rc_l;                                                                                             \
-            KERNEL<<<dim3(MAXKP / (16 * (NWV) * QT), npairs), 64 * (NWV), (LDSB), ctx->stream>>>(fq->d_bits, fq->d_pop, fq->d_n, ft->d_bits, \
-                                                                                         ft->d_pop, ft->d_n, d_pairs, d_pairs + npairs, m_idx, m_dist); \
-        } while (0)
-        const size_t ldsi8 = (size_t)2 * 64 * MT_ROW + 2 * 64 * sizeof(uint32_t);
-#define UWIP_LAUNCH_MATCH_F4(KERNEL, NWV, LDSB)                                                                                \
-        do {                                                                                                                   \
-            int rc_l = uwip_lds_optin(ctx, #KERNEL, (const void *)KERNEL, (LDSB));                                             \
-            if (rc_l) return rc_l;                                                                                             \
-            KERNEL<<<dim3(MAXKP / (16 * (NWV) * QT), npairs), 64 * (NWV), (LDSB), ctx->stream>>>(fq->d_nib, fq->d_pop, fq->d_n, ft->d_nib, \
-                                                                                         ft->d_pop, ft->d_n, d_pairs, d_pairs + npairs, m_idx, m_dist); \
-        } while (0)
-        const size_t ldsf4 = (size_t)2 * 64 * F4_ROW + 2 * 64 * sizeof(float), ldsf8 = (size_t)2 * 128 * F4_ROW + 2 * 128 * sizeof(float);
-        switch (form) {                  // unknown values run the default
-        case 3: UWIP_LAUNCH_MATCH((k_ov_match_sp<QT, 8, 4>), 8, ldsi8); break;      // round 4's i8 form
-        case 5: UWIP_LAUNCH_MATCH_F4((k_ov_match_f4<QT, 8, 8>), 8, ldsf8); break;   // FP4, 128 train columns per barrier
-        case 6: UWIP_LAUNCH_MATCH_F4((k_ov_match_f4<QT, 4, 4>), 4, ldsf4); break;   // FP4, 4-wave blocks
-        default: UWIP_LAUNCH_MATCH_F4((k_ov_match_f4<QT, 8, 4>), 8, ldsf4); break;  // FP4 operands (round 5)
-        }
-#undef UWIP_LAUNCH_MATCH_F4
-#undef UWIP_LAUNCH_MATCH
-        UWIP_HIP(ctx, hipGetLastError());
-    }
-    {
-        uwip_kscope ks(ctx, "k_ov_geometry");
-        const size_t lds = (size_t)MAXKP * 16 + MAXKP + (size_t)TH * MASK_WORDS * 4 + (size_t)TH * 4;
-        int rc = uwip_lds_optin(ctx, "k_ov_geometry", (const void *)k_ov_geometry, lds);
-        if (rc) return rc;
-        k_ov_geometry<<<npairs, 256, lds, ctx->stream>>>(fq->d_kp, ft->d_kp, fq->d_n, ft->d_n, d_pairs, d_pairs + npairs, m_idx, m_dist,
-                                                        fq->w, fq->h, videoWidth, videoHeight, seed, min_inliers, d_ratio, info, d_H);
-        UWIP_HIP(ctx, hipGetLastError());
-    }
-    return UWIP_OK;
+    return launch_match(ctx, fq, ft, d_pairs, d_pairs + npairs, nullptr, npairs, videoWidth, videoHeight, seed, min_inliers, d_ratio,
+                        info, d_H, m_idx, m_dist);
 }
 
 // overlapArea(Mat H), videostrip.cpp:291-319, for n homographies (device, row-major 3x3 doubles)
@@ -2395,5 +2412,58 @@ UWIP_API int uwip_features_copy(uwip_ctx *ctx, const uwip_features *src, int src
     UWIP_HIP(ctx, hipMemcpyAsync(dst->d_nib + d * DESC_NIBW, src->d_nib + s * DESC_NIBW, (size_t)MAXKP * DESC_NIBW * 4, hipMemcpyDeviceToDevice, ctx->stream));
     UWIP_HIP(ctx, hipMemcpyAsync(dst->d_pop + d, src->d_pop + s, sizeof(int32_t) * MAXKP, hipMemcpyDeviceToDevice, ctx->stream));
     UWIP_HIP(ctx, hipMemcpyAsync(dst->d_n + dst_slot, src->d_n + src_slot, sizeof(int32_t), hipMemcpyDeviceToDevice, ctx->stream));
+    return UWIP_OK;
+}
+
+// ---- the key-frame chain's device-side entry points (pipe.cpp, kf_chain.hpp) -------------------------------------
+
+int uwip_overlap_match_dev(uwip_ctx *ctx, const uwip_features *f, const int32_t *d_pq, const int32_t *d_pt, const int32_t *d_npairs,
+                           int npairs, int videoWidth, int videoHeight, uint32_t seed, unsigned flags, float *d_ratio, int32_t *d_info,
+                           int32_t *m_idx, int32_t *m_dist)
+{
+    if (int rc_e = uwip_enter(ctx)) return rc_e;
+    UWIP_REQUIRE(ctx, f && f->ctx == ctx && f->w > 0, "bad feature set");
+    UWIP_REQUIRE(ctx, npairs >= 0 && npairs <= 65535, "npairs out of range");
+    UWIP_REQUIRE(ctx, d_pq && d_pt && d_ratio && d_info && m_idx && m_dist, "null buffer");
+    if (npairs == 0) return UWIP_OK;
+    const int min_inliers = (flags & UWIP_OVERLAP_MIN6) ? MIN_INLIERS_STRICT : MIN_INLIERS;
+    return launch_match(ctx, f, f, d_pq, d_pt, d_npairs, npairs, videoWidth, videoHeight, seed, min_inliers, d_ratio, d_info, nullptr,
+                        m_idx, m_dist);
+}
+
+size_t uwip_overlap_match_scratch_bytes(int npairs) { return sizeof(int32_t) * 2 * MAXKP * (size_t)npairs; }
+
+namespace {
+// job j = blockIdx.y copies slot src[j] to slot dst_j (src[j] < 0: nothing); the slot indices come from device memory
+__global__ __launch_bounds__(256) void k_kf_slot_copy(Keypoint *kp, uint8_t *desc, int8_t *bits, uint32_t *nib, int32_t *pop,
+                                                      int32_t *nkp, int capacity, const int32_t *__restrict__ src, int dst0, int dst1)
+{
+    const int s = src[blockIdx.y], d = blockIdx.y == 0 ? dst0 : dst1;
+    if (s < 0 || s >= capacity || s == d) return;
+    struct Part { uint4 *base; size_t n16; };        // per-slot bytes / 16 of each array
+    const Part parts[5] = {{reinterpret_cast<uint4 *>(kp), sizeof(Keypoint) * MAXKP / 16},
+                           {reinterpret_cast<uint4 *>(desc), (size_t)MAXKP * DESC_BYTES / 16},
+                           {reinterpret_cast<uint4 *>(bits), (size_t)MAXKP * DESC_K / 16},
+                           {reinterpret_cast<uint4 *>(nib), (size_t)MAXKP * DESC_NIBW * 4 / 16},
+                           {reinterpret_cast<uint4 *>(pop), (size_t)MAXKP * 4 / 16}};
+    const size_t stride = (size_t)gridDim.x * blockDim.x;
+    for (int a = 0; a < 5; ++a) {
+        const uint4 *from = parts[a].base + (size_t)s * parts[a].n16;
+        uint4 *to = parts[a].base + (size_t)d * parts[a].n16;
+        for (size_t k = (size_t)blockIdx.x * blockDim.x + threadIdx.x; k < parts[a].n16; k += stride) to[k] = from[k];
+    }
+    if (blockIdx.x == 0 && threadIdx.x == 0) nkp[d] = nkp[s];
+}
+}  // namespace
+
+int uwip_features_copy_dev(uwip_ctx *ctx, uwip_features *f, const int32_t *d_src, int dst0, int dst1)
+{
+    if (int rc_e = uwip_enter(ctx)) return rc_e;
+    UWIP_REQUIRE(ctx, f && f->ctx == ctx, "bad feature set");
+    UWIP_REQUIRE(ctx, dst0 >= 0 && dst0 < f->capacity && dst1 >= 0 && dst1 < f->capacity && dst0 != dst1, "slot out of range");
+    uwip_kscope ks(ctx, "k_kf_slot_copy");
+    k_kf_slot_copy<<<dim3(64, 2), 256, 0, ctx->stream>>>(f->d_kp, f->d_desc, f->d_bits, f->d_nib, f->d_pop, f->d_n, f->capacity, d_src,
+                                                       dst0, dst1);
+    UWIP_HIP(ctx, hipGetLastError());
     return UWIP_OK;
 }

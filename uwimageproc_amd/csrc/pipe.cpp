@@ -35,6 +35,23 @@ struct uwip_pipe {
     const uint8_t *last_frames = nullptr;
     const float *last_ratio = nullptr;
     const int32_t *last_info = nullptr;
+    int eos_valid = -1;                                // uwip_pipe_end_of_stream: the next step is the last, with this many frames
+    // key-frame mode (uwip_pipe_keyframe_chain; kf_chain.hpp): one device block holds everything the chain carries
+    struct Keyframe {
+        bool on = false;
+        uwip_keyframe_config kc{};
+        int R = 0, P0 = 0, oh = 0, ow = 0;
+        bool started = false;                          // the stream's frame 0 has been seen (host's view)
+        int32_t base = 0;                              // stream index of the next step's frame 0
+        uint32_t consumed = 0;                         // rows handed out by uwip_pipe_keyframes
+        uint8_t *block = nullptr;
+        uwip_kf::State *state = nullptr;
+        int32_t *fb_key = nullptr, *fb_start = nullptr, *fb_list = nullptr, *fb_n = nullptr, *r0 = nullptr;
+        float *out_ratio = nullptr, *blur = nullptr;
+        int32_t *out_info = nullptr, *midx = nullptr, *mdist = nullptr;
+        uwip_keyframe_row *ring = nullptr;
+        uint8_t *res = nullptr;                        // the batch at the working size (calcBlur's input, main.cpp:311)
+    } kf;
 
     int fail(int code, const char *what)
     {
@@ -76,6 +93,8 @@ int check_io(uwip_pipe *p, const uwip_batch_u8 *b, const char *what)
     return UWIP_OK;
 }
 
+int run_keyframe(uwip_pipe *p, const uwip_batch_u8 *out, float *d_ratio, int32_t *d_info);
+
 // the chain itself (pipeline stage definitions: uwip.h)
 int run_stages(uwip_pipe *p, unsigned stages, const uwip_batch_u8 *in, const uwip_batch_u8 *out, float *d_ratio, int32_t *d_info)
 {
@@ -100,6 +119,7 @@ int run_stages(uwip_pipe *p, unsigned stages, const uwip_batch_u8 *in, const uwi
     }
     if (stages & UWIP_PIPE_OVERLAP) {
         if (!d_ratio) return p->fail(UWIP_ERR_INVALID, "the overlap stage needs d_ratio");
+        if (p->kf.on) return run_keyframe(p, out, d_ratio, d_info);
         if (!p->have_prev) {
             // first batch: frame 0 is its own key frame (main.cpp:284-297 takes the first frame as key frame)
             uwip_batch_u8 first = *out;
@@ -116,8 +136,59 @@ int run_stages(uwip_pipe *p, unsigned stages, const uwip_batch_u8 *in, const uwi
                                    c.videoWidth ? c.videoWidth : c.cols, c.videoHeight ? c.videoHeight : c.rows, c.seed, c.match_flags,
                                    d_ratio, d_info, nullptr, nullptr, nullptr);
         if (rc) return p->from_ctx(rc);
+        if (p->eos_valid >= 0) { p->have_prev = false; p->eos_valid = -1; }
     }
     return UWIP_OK;
+}
+
+// The overlap stage in key-frame mode (kf_chain.hpp): detect into slots 1..F, blur, round 0's fixed pair list, then R
+// rounds of (walker, matcher on the list the walker wrote), the last walker call, and the carry of the key / window
+// candidate into slots 0 / F + 1.  Every count and slot index past round 0 is read on the device: nothing here waits.
+int run_keyframe(uwip_pipe *p, const uwip_batch_u8 *out, float *d_ratio, int32_t *d_info)
+{
+    uwip_ctx *ctx = p->ctx;
+    const uwip_pipe_config &c = p->cfg;
+    uwip_pipe::Keyframe &k = p->kf;
+    const int F = c.frames;
+    const int vw = c.videoWidth ? c.videoWidth : c.cols, vh = c.videoHeight ? c.videoHeight : c.rows;
+    int rc;
+    if ((rc = uwip_overlap_detect_ex(ctx, out, p->feats, 1, c.detect_flags))) return p->from_ctx(rc);
+    // the stream's frame 0 is the first key frame (main.cpp:284-297): slot 0 holds the key at the start of a step
+    if (!k.started && (rc = uwip_features_copy(ctx, p->feats, 1, p->feats, 0))) return p->from_ctx(rc);
+    // calcBlur(res_frame), main.cpp:311,338,355
+    uwip_batch_u8 rb;
+    rb.data = k.res; rb.step = (size_t)k.ow * 3; rb.frame_stride = rb.step * k.oh;
+    rb.rows = k.oh; rb.cols = k.ow; rb.channels = 3; rb.frames = F;
+    if ((rc = uwip_resize_bgr(ctx, out, &rb)) || (rc = uwip_calcBlur(ctx, &rb, k.blur))) return p->from_ctx(rc);
+    if ((rc = uwip_overlap_match_dev(ctx, p->feats, k.r0, k.r0 + k.P0, nullptr, k.P0, vw, vh, c.seed, c.match_flags, k.out_ratio,
+                                     k.out_info, k.midx, k.mdist)))
+        return p->from_ctx(rc);
+    const bool last = p->eos_valid >= 0;
+    uwip_kf::Batch b;
+    b.F = F; b.D = k.kc.lookback; b.kWindow = k.kc.kWindow; b.valid = last ? p->eos_valid : F; b.base = k.base;
+    b.rounds = k.R; b.max_rows = k.kc.max_rows; b.minOverlap = k.kc.minOverlap; b.first = k.started ? 0 : 1; b.last = last ? 1 : 0;
+    uwip_kf::Bufs u;
+    u.out_ratio = k.out_ratio; u.out_info = k.out_info; u.blur = k.blur; u.ratio = d_ratio; u.info = d_info; u.ring = k.ring;
+    u.fb_key = k.fb_key; u.fb_start = k.fb_start; u.fb_q = k.fb_list; u.fb_t = k.fb_list + F; u.fb_n = k.fb_n;
+    if ((rc = uwip_kf_walk(ctx, b, k.state, u, 0))) return p->from_ctx(rc);
+    for (int r = 1; r <= k.R; ++r) {
+        const size_t at = (size_t)k.P0 + (size_t)(r - 1) * F;
+        if ((rc = uwip_overlap_match_dev(ctx, p->feats, u.fb_q, u.fb_t, k.fb_n, F, vw, vh, c.seed, c.match_flags, k.out_ratio + at,
+                                         k.out_info + 8 * at, k.midx, k.mdist)))
+            return p->from_ctx(rc);
+        if ((rc = uwip_kf_walk(ctx, b, k.state, u, r))) return p->from_ctx(rc);
+    }
+    if ((rc = uwip_features_copy_dev(ctx, p->feats, &k.state->carry_key, 0, F + 1))) return p->from_ctx(rc);
+    k.started = true;
+    k.base += F;
+    if (last) { k.started = false; k.base = 0; p->eos_valid = -1; }
+    return UWIP_OK;
+}
+
+void kf_free(uwip_pipe *p)
+{
+    uwip_free(p->ctx, p->kf.block);
+    p->kf = uwip_pipe::Keyframe();
 }
 
 int ensure_host_state(uwip_pipe *p)
@@ -242,6 +313,7 @@ UWIP_API int uwip_pipe_destroy(uwip_pipe *p)
     if (p->own_copier) uwip_copier_destroy(p->copier);
     if (p->own_staging) uwip_free(p->ctx, p->staging);
     uwip_features_destroy(p->feats);
+    kf_free(p);
     uwip_free(p->ctx, p->v);
     delete p;
     return UWIP_OK;
@@ -343,6 +415,9 @@ UWIP_API int uwip_pipe_reset(uwip_pipe *p)
 {
     if (!p) return UWIP_ERR_INVALID;
     p->have_prev = false;
+    p->eos_valid = -1;
+    p->kf.started = false;
+    p->kf.base = 0;
     return UWIP_OK;
 }
 
@@ -360,5 +435,120 @@ UWIP_API int uwip_pipe_device_results(uwip_pipe *p, const uint8_t **d_v, const u
     if (d_frames) *d_frames = p->last_frames;
     if (d_ratio) *d_ratio = p->last_ratio;
     if (d_info) *d_info = p->last_info;
+    return UWIP_OK;
+}
+
+// ---- key-frame mode ----------------------------------------------------------------------------------------------
+
+UWIP_API int uwip_keyframe_config_default(uwip_keyframe_config *kc)
+{
+    if (!kc) return UWIP_ERR_INVALID;
+    std::memset(kc, 0, sizeof *kc);
+    kc->minOverlap = uwip_kf::OVERLAP_MIN;      // videostrip.hpp:50
+    kc->kWindow = 11;                           // videostrip.hpp:51
+    kc->lookback = 8;                           // the cheapest D measured (tools/keyframe_cost.py)
+    kc->max_rows = 4096;
+    return UWIP_OK;
+}
+
+UWIP_API int uwip_keyframe_max_rounds(const uwip_keyframe_config *kc, int frames)
+{
+    if (!kc || !uwip_kf::config_ok(*kc) || frames < 1) return -1;
+    return uwip_kf::max_rounds(frames, kc->lookback, kc->kWindow);
+}
+
+UWIP_API int uwip_pipe_keyframe_chain(uwip_pipe *p, const uwip_keyframe_config *kc)
+{
+    if (!p) return UWIP_ERR_INVALID;
+    if (!kc || !uwip_kf::config_ok(*kc)) return p->fail(UWIP_ERR_INVALID, "bad key-frame configuration");
+    if (p->have_prev || p->kf.started || p->eos_valid >= 0)
+        return p->fail(UWIP_ERR_INVALID, "uwip_pipe_keyframe_chain: before the first step or right after uwip_pipe_reset");
+    if (int rc_e = uwip_enter(p->ctx)) return p->from_ctx(rc_e);
+    const int F = p->cfg.frames;
+    const int P0 = uwip_kf::round0_pairs(F, kc->lookback), R = uwip_kf::max_rounds(F, kc->lookback, kc->kWindow);
+    if (P0 > 65535 || F + 2 > 4096) return p->fail(UWIP_ERR_INVALID, "batch too large for key-frame mode (pair list > 65535)");
+    int rc = uwip_pipe_sync(p);                 // the feature slots and the chain's buffers are re-made
+    if (rc) return rc;
+    kf_free(p);
+    uwip_features_destroy(p->feats);
+    p->feats = nullptr;
+    if ((rc = uwip_features_create(p->ctx, F + 2, &p->feats))) return p->from_ctx(rc);
+    uwip_pipe::Keyframe &k = p->kf;
+    k.kc = *kc; k.R = R; k.P0 = P0;
+    if ((rc = uwip_overlap_working_size(p->cfg.rows, p->cfg.cols, &k.oh, &k.ow))) return p->fail(rc, "uwip_overlap_working_size");
+    const size_t npo = (size_t)P0 + (size_t)R * F, scratch = uwip_overlap_match_scratch_bytes(std::max(P0, F));
+    size_t off = 0;
+    auto take = [&](size_t bytes) { const size_t at = off; off += align256(bytes); return at; };
+    const size_t o_state = take(sizeof(uwip_kf::State)), o_fbk = take(4 * (size_t)(R + 1)), o_fbs = take(4 * (size_t)(R + 1)),
+                 o_fbl = take(4 * 2 * (size_t)F), o_fbn = take(4), o_r0 = take(4 * 2 * (size_t)P0), o_ratio = take(4 * npo),
+                 o_info = take(32 * npo), o_midx = take(scratch), o_mdist = take(scratch), o_blur = take(4 * (size_t)F),
+                 o_ring = take(sizeof(uwip_keyframe_row) * (size_t)kc->max_rows),
+                 o_res = take((size_t)F * k.oh * k.ow * 3);
+    void *d = nullptr;
+    if ((rc = uwip_malloc(p->ctx, off, &d))) return p->from_ctx(rc);
+    uint8_t *base = (uint8_t *)d;
+    k.block = base;
+    k.state = (uwip_kf::State *)(base + o_state);
+    k.fb_key = (int32_t *)(base + o_fbk); k.fb_start = (int32_t *)(base + o_fbs);
+    k.fb_list = (int32_t *)(base + o_fbl); k.fb_n = (int32_t *)(base + o_fbn); k.r0 = (int32_t *)(base + o_r0);
+    k.out_ratio = (float *)(base + o_ratio); k.out_info = (int32_t *)(base + o_info);
+    k.midx = (int32_t *)(base + o_midx); k.mdist = (int32_t *)(base + o_mdist);
+    k.blur = (float *)(base + o_blur); k.ring = (uwip_keyframe_row *)(base + o_ring); k.res = base + o_res;
+    // round 0's fixed list (kf_chain.hpp round0_index): (i, slot 0) for every frame, then (i, i - d) for d = 1..D
+    std::vector<int32_t> r0(2 * (size_t)P0);
+    uwip_kf::round0_list(F, kc->lookback, r0.data(), r0.data() + P0);
+    uwip_kf::State st{};
+    st.carry_key = st.carry_best = -1;
+    if ((rc = uwip_memcpy_h2d(p->ctx, k.r0, r0.data(), sizeof(int32_t) * r0.size())) ||
+        (rc = uwip_memcpy_h2d(p->ctx, k.state, &st, sizeof st))) {
+        kf_free(p);
+        return p->from_ctx(rc);
+    }
+    k.on = true;
+    return UWIP_OK;
+}
+
+UWIP_API int uwip_pipe_end_of_stream(uwip_pipe *p, int valid)
+{
+    if (!p) return UWIP_ERR_INVALID;
+    if (valid < 1 || valid > p->cfg.frames) return p->fail(UWIP_ERR_INVALID, "valid must be in [1, frames]");
+    p->eos_valid = valid;
+    return UWIP_OK;
+}
+
+UWIP_API int uwip_pipe_keyframes(uwip_pipe *p, uwip_keyframe_row *h_rows, int cap, int *n)
+{
+    if (!p) return UWIP_ERR_INVALID;
+    if (!n || cap < 0 || (cap > 0 && !h_rows)) return p->fail(UWIP_ERR_INVALID, "null buffer or negative capacity");
+    *n = 0;
+    if (!p->kf.on) return p->fail(UWIP_ERR_INVALID, "the pipe is not in key-frame mode (uwip_pipe_keyframe_chain)");
+    if (int rc_e = uwip_enter(p->ctx)) return p->from_ctx(rc_e);
+    uwip_pipe::Keyframe &k = p->kf;
+    const hipError_t he = uwip_stream_wait(p->ctx);
+    if (he != hipSuccess) return p->fail(UWIP_ERR_HIP, hipGetErrorString(he));
+    uwip_kf::State st;
+    if (hipMemcpy(&st, k.state, sizeof st, hipMemcpyDeviceToHost) != hipSuccess) return p->fail(UWIP_ERR_HIP, "hipMemcpy");
+    if (st.err) {
+        // reported once; the chain stays stopped until the next stream (uwip_pipe_reset / uwip_pipe_end_of_stream)
+        const int32_t zero = 0;
+        if (hipMemcpy(&k.state->err, &zero, sizeof zero, hipMemcpyHostToDevice) != hipSuccess) return p->fail(UWIP_ERR_HIP, "hipMemcpy");
+        return p->fail(UWIP_ERR_INVALID, "key-frame chain: a batch was not resolved within the round bound; the stream's chain stopped there");
+    }
+    const uint32_t M = (uint32_t)k.kc.max_rows;
+    if (st.total - k.consumed > M) {
+        const uint32_t lost = st.total - k.consumed - M;
+        k.consumed = st.total - M;
+        return p->fail(UWIP_ERR_INVALID, (std::string("uwip_pipe_keyframes: the caller fell behind the row ring: ") +
+                                          std::to_string(lost) + " rows were overwritten").c_str());
+    }
+    const uint32_t m = std::min<uint32_t>(st.total - k.consumed, (uint32_t)cap);
+    for (uint32_t done = 0; done < m;) {
+        const uint32_t at = (k.consumed + done) % M, run = std::min(m - done, M - at);
+        if (hipMemcpy(h_rows + done, k.ring + at, sizeof(uwip_keyframe_row) * run, hipMemcpyDeviceToHost) != hipSuccess)
+            return p->fail(UWIP_ERR_HIP, "hipMemcpy");
+        done += run;
+    }
+    k.consumed += m;
+    *n = (int)m;
     return UWIP_OK;
 }

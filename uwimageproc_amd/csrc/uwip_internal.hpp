@@ -9,6 +9,7 @@
 #include <string>
 #include <vector>
 #include "../../include/uwip.h"
+#include "kf_chain.hpp"
 
 #define UWIP_API extern "C" __attribute__((visibility("default")))
 
@@ -130,6 +131,17 @@ inline int uwip_test_force_cl()
 }
 // hipFuncSetAttribute(MaxDynamicSharedMemorySize) once per (context, kernel)
 int uwip_lds_optin(uwip_ctx *ctx, const char *name, const void *func, size_t bytes);
+// overlap.hip, for the key-frame chain (kf_chain.hpp): uwip_overlap_match_ex on a pair list already in device memory, d_pq /
+// d_pt [npairs] slots of `f` (query, train); d_npairs (null: all npairs) a pair count the device wrote, blocks at or beyond
+// it return at once.  m_idx / m_dist: caller scratch of uwip_overlap_match_scratch_bytes(npairs) bytes each.
+int uwip_overlap_match_dev(uwip_ctx *ctx, const uwip_features *f, const int32_t *d_pq, const int32_t *d_pt, const int32_t *d_npairs,
+                           int npairs, int videoWidth, int videoHeight, uint32_t seed, unsigned flags, float *d_ratio, int32_t *d_info,
+                           int32_t *m_idx, int32_t *m_dist);
+size_t uwip_overlap_match_scratch_bytes(int npairs);
+// copy slot d_src[0] to slot dst0 and slot d_src[1] to slot dst1 of `f`; the source slots are read on the device (< 0: no copy)
+int uwip_features_copy_dev(uwip_ctx *ctx, uwip_features *f, const int32_t *d_src, int dst0, int dst1);
+// kf_chain.hip: one walker call of the key-frame chain (kf_chain.hpp) on the device
+int uwip_kf_walk(uwip_ctx *ctx, const uwip_kf::Batch &b, uwip_kf::State *d_state, const uwip_kf::Bufs &u, int round);
 
 #define UWIP_HIP(ctx, expr)                                                          \
     do {                                                                             \

@@ -13,7 +13,8 @@ Stage definitions (DESIGN.md "the pipe"):
              sweep = aclahe.cpp:160-193, parameter choice :66-129) -> CLAHE(CL,(BS,BS)) on the unfiltered V
              (python/main.py:19-20) -> back to BGR (aclahe.cpp:216)
   overlap    calcOverlap of every frame against its predecessor (videostrip.cpp:192-289),
-             the last frame's features carried into the next batch
+             the last frame's features carried into the next batch; or, with ``keyframes=``, videostrip's key-frame
+             selector (main.cpp:284-394) decided on the device over the stream of enhanced frames (``keyframe_rows``)
 """
 from __future__ import annotations
 
@@ -21,12 +22,45 @@ import ctypes as C
 
 import torch
 
-from ._native import Context, Copier, PipeConfig, UwipError, batch_of
+from ._native import (KF_BLUR_FN, KF_OVERLAP_FN, Context, Copier, KeyframeConfig, KeyframeRow, PipeConfig, UwipError, batch_of,
+                      lib)
 
 DEHAZE_FULL, DEHAZE_GUARD_S = 1, 2              # uwip.h
 OVERLAP_MIN6 = 8
 ACLAHE_PREFILTER, ACLAHE_ASYNC = 1, 4
 PIPE_DEHAZE, PIPE_HISTRETCH, PIPE_ACLAHE, PIPE_OVERLAP, PIPE_ALL = 1, 2, 4, 8, 15
+
+
+def keyframe_config(minOverlap=None, kWindow=None, lookback=None, max_rows=None) -> KeyframeConfig:
+    """``uwip_keyframe_config``: the library's defaults (0.4, 11: videostrip.hpp:50-51) with the given fields replaced."""
+    kc = KeyframeConfig()
+    lib().uwip_keyframe_config_default(C.byref(kc))
+    for name, v in (("minOverlap", minOverlap), ("kWindow", kWindow), ("lookback", lookback), ("max_rows", max_rows)):
+        if v is not None:
+            setattr(kc, name, v)
+    return kc
+
+
+def _row(r: KeyframeRow):
+    return (r.id, r.frame, r.index, r.overlap, r.blur)
+
+
+def keyframe_chain_host(overlap, blur, n_frames: int, batch: int, **kf):
+    """The pipe's key-frame chain (csrc/kf_chain.hpp) with its batch / round scheme, on the host: overlap(key, frame) and
+    blur(frame) give the values the device would compute.  Returns (rows [(id, frame, index, overlap, blur)], fallback
+    rounds per batch).  uwip_keyframe_chain_host; needs no device."""
+    kc = keyframe_config(**kf)
+    ov_cb = KF_OVERLAP_FN(lambda _u, k, f: float(overlap(k, f)))
+    bl_cb = KF_BLUR_FN(lambda _u, f: float(blur(f)))
+    cap = n_frames + 1
+    rows = (KeyframeRow * cap)()
+    n = C.c_int(0)
+    nb = max(1, -(-n_frames // batch))
+    rounds = (C.c_int32 * nb)()
+    rc = lib().uwip_keyframe_chain_host(C.byref(kc), int(n_frames), int(batch), ov_cb, bl_cb, None, rows, cap, C.byref(n), rounds)
+    if rc:
+        raise UwipError(rc, "uwip_keyframe_chain_host")
+    return [_row(rows[i]) for i in range(n.value)], list(rounds)[:-(-n_frames // batch)]
 
 
 class _DevView:
@@ -39,10 +73,15 @@ class _DevView:
 
 class FramePipe:
     """``uwip_pipe`` with the library's defaults = the reference's rules; the two deviations are opt-in: ``guard_s``
-    (UWIP_DEHAZE_GUARD_S) and ``min6`` (UWIP_OVERLAP_MIN6)."""
+    (UWIP_DEHAZE_GUARD_S) and ``min6`` (UWIP_OVERLAP_MIN6).  ``keyframes`` = dict(minOverlap=, kWindow=, lookback=,
+    max_rows=) (any subset; {} = the reference's 0.4 / 11) switches the overlap stage to videostrip's key-frame selector
+    (uwip_pipe_keyframe_chain): ``keyframe_rows()`` returns the rows, ``end_of_stream(valid)`` marks the last batch.  In
+    key-frame mode the host-buffer form (``run_host``) must be the pipe's first step: its staging area is made with a new
+    C pipe, which keeps the key-frame configuration and a pending end-of-stream mark but not a chain already under way."""
 
     def __init__(self, device: int, frames: int, rows: int, cols: int, letters: str = "RGB", w: int = 15,
-                 video_size=None, seed: int = 1, copier: "Copier | None" = None, guard_s: bool = False, min6: bool = False):
+                 video_size=None, seed: int = 1, copier: "Copier | None" = None, guard_s: bool = False, min6: bool = False,
+                 keyframes: "dict | None" = None):
         self.dev = torch.device("cuda", device)
         torch.cuda.set_device(self.dev)
         # share torch's current stream so torch events / synchronize cover our kernels
@@ -76,12 +115,42 @@ class FramePipe:
         self.h_cl = (C.c_int32 * frames)()
         self._params = None
         self._k = 0
+        self._kc = keyframe_config(**keyframes) if keyframes is not None else None
+        self._eos = None             # a pending uwip_pipe_end_of_stream mark (the C pipe holds it too)
+        self._chain_used = False     # an overlap stage has run in key-frame mode: the C pipe holds chain state and rows
         self._create()
 
     def _create(self):
         h = C.c_void_p()
         self.ctx.call("uwip_pipe_create", C.byref(self._cfg), self.copier._h if self.copier is not None else None, C.byref(h))
         self._p = h
+        if self._kc is not None:
+            self._call("uwip_pipe_keyframe_chain", C.byref(self._kc))
+        if self._eos is not None:
+            self._call("uwip_pipe_end_of_stream", self._eos)
+
+    def _overlap_ran(self):
+        # the step that ran the overlap stage consumed the end-of-stream mark
+        self._eos = None
+        self._chain_used = self._chain_used or self._kc is not None
+
+    # ---- key-frame mode (uwip_pipe_keyframe_chain) ----------------------------------------------------------
+    def end_of_stream(self, valid: int):
+        """The next step is the stream's last and only its first `valid` frames are real (uwip_pipe_end_of_stream)."""
+        self._call("uwip_pipe_end_of_stream", int(valid))
+        self._eos = int(valid)
+
+    def keyframe_rows(self):
+        """Rows [(id, frame, index, overlap, blur)] closed since the last call (waits for the stream)."""
+        out = []
+        cap = 256
+        buf = (KeyframeRow * cap)()
+        while True:
+            n = C.c_int(0)
+            self._call("uwip_pipe_keyframes", buf, cap, C.byref(n))
+            out += [_row(buf[i]) for i in range(n.value)]
+            if n.value < cap:
+                return out
 
     def _call(self, name, *args):
         rc = getattr(self._l, name)(self._p, *args)
@@ -109,6 +178,8 @@ class FramePipe:
         wb = batch_of(self.work)
         self._call("uwip_pipe_stages", mask, C.byref(sb) if sb is not None else None, C.byref(wb),
                    C.c_void_p(self.ratio.data_ptr()), C.c_void_p(self.info.data_ptr()))
+        if mask & PIPE_OVERLAP:
+            self._overlap_ran()
         if mask & PIPE_ACLAHE:
             self._params = None
 
@@ -144,6 +215,7 @@ class FramePipe:
     def have_prev(self, value):
         assert not value
         self._call("uwip_pipe_reset")
+        self._eos = None
 
     @property
     def v(self):
@@ -172,8 +244,12 @@ class FramePipe:
 
     def _host_state(self):
         if self._staging is None:
-            # uwip_pipe_config.d_staging must be known at creation: the pipe is made anew (nothing has been carried yet)
+            # uwip_pipe_config.d_staging must be known at creation: the pipe is made anew (nothing has been carried yet;
+            # _create applies the key-frame configuration and a pending end-of-stream mark again)
             assert self._k == 0
+            if self._chain_used:
+                raise UwipError(1, "key-frame mode: the host-buffer form must be the pipe's first step (the pipe is re-made "
+                                   "for it, which would drop the chain and its unread rows)")
             n = self._l.uwip_pipe_staging_bytes(C.byref(self._cfg))
             self._staging = torch.empty((n,), dtype=torch.uint8, device=self.dev)
             self._cfg.d_staging = self._staging.data_ptr()
@@ -199,6 +275,7 @@ class FramePipe:
         self._call("uwip_pipe_step_host", C.c_void_p(h_in.ctypes.data), C.c_void_p(h_out.ctypes.data),
                    C.c_void_p(h_ratio.ctypes.data) if h_ratio is not None else None,
                    C.c_void_p(prefetch.ctypes.data) if prefetch is not None else None, t)
+        self._overlap_ran()
         slot = self._k % 2
         self.work, self.ratio, self.info = self._h_work[slot], self._h_ratio[slot], self._h_info[slot]
         self._k += 1
@@ -217,5 +294,6 @@ class FramePipe:
         self.work, self.ratio, self.info = self._own
         sb, wb = batch_of(src), batch_of(self.work)
         self._call("uwip_pipe_step", C.byref(sb), C.byref(wb), C.c_void_p(self.ratio.data_ptr()), C.c_void_p(self.info.data_ptr()))
+        self._overlap_ran()
         self._params = None
         return self.work, self.ratio
