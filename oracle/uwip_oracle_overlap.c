@@ -419,7 +419,7 @@ static int detect(const scale_space *S, orc_keypoint *kps /* OV_MAXKP */, int fl
  * sector is two cross products against the sector's boundary unit vectors (tables below), and the result is the unit
  * vector (co, si) itself -- only +, *, /, sqrt, all correctly rounded on both sides, so the device matches bit for bit.
  * Sums run over the samples in raster order (i = x offset outer, j = y offset inner). */
-/* ORIENT-TABLES-BEGIN (generated by tools/gen_orient_tables.py, identical text in csrc/overlap.hip) */
+/* ORIENT-TABLES-BEGIN (generated by tools/gen_orient_tables.py, identical text in csrc/overlap_describe.hip) */
 static const float OV_GAUSS25[7][7] = {
     {1.0f, 0.923116326f, 0.726149023f, 0.486752242f, 0.27803731f, 0.135335281f, 0.0561347641f},
     {0.923116326f, 0.852143764f, 0.670320034f, 0.449328959f, 0.256660789f, 0.12493021f, 0.0518189184f},

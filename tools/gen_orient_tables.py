@@ -1,6 +1,6 @@
 """Constant tables of the keypoint orientation (overlap stage): the 7x7 Gaussian weights
 exp(-(i^2+j^2)/(2*2.5^2)) and, for the 42 sector starts a_k = 0.15 k rad, the unit vectors of a_k and a_k + pi/3.
-The same literal text is pasted into oracle/uwip_oracle_overlap.c and uwimageproc_amd/csrc/overlap.hip (between the
+The same literal text is pasted into oracle/uwip_oracle_overlap.c and uwimageproc_amd/csrc/overlap_describe.hip (between the
 ORIENT-TABLES markers) so that both sides hold bit-identical floats:   python tools/gen_orient_tables.py --write"""
 import os, re, sys
 import numpy as np
@@ -36,7 +36,7 @@ def text(prefix):
 
 
 if __name__ == "__main__":
-    targets = [("oracle/uwip_oracle_overlap.c", "OV_", ""), ("uwimageproc_amd/csrc/overlap.hip", "D_", "__device__ ")]
+    targets = [("oracle/uwip_oracle_overlap.c", "OV_", ""), ("uwimageproc_amd/csrc/overlap_describe.hip", "D_", "__device__ ")]
     for path, prefix, qual in targets:
         t = text(prefix)
         if qual:
