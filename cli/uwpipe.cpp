@@ -4,13 +4,15 @@
 //   calcOverlap of every frame against its predecessor (modules/videostrip/src/videostrip.cpp:192-289)
 // on the frames of a Motion-JPEG .avi or of a frame list, in batches through page-locked host buffers
 // (uwip_pipe_step_host: batch k + 1 is uploaded and batch k - 1 leaves while batch k's kernels run).
-//   uwpipe [-b N] [-c LETTERS] [-w N] [--guard-s] [--min6] [--relative-threshold] [--png]
+//   uwpipe [-b N] [-c LETTERS] [-w N] [--guard-s] [--min6] [--relative-threshold] [--png] [--device-jpeg]
 //          [--keyframes [-k N] [-p X] [--lookback D]] <video.avi | frame_list.txt> <output_prefix>
 // writes <prefix>NNNN.jpg (the enhanced frames) and <prefix>uwpipe_report.txt (TSV: ID, Filename, Overlap, BS, CL).
 // --keyframes: the overlap stage runs videostrip's key-frame selector (main.cpp:284-394) on the enhanced frames, on the
 // device (uwip_pipe_keyframe_chain); <prefix>videostrip_report.txt gets its rows with the reference's columns (ID, Frame,
 // Filename, Overlap, Blur), Filename = the enhanced frame that is the key frame.  Overlap in uwpipe_report.txt is then the
 // overlap against the current key frame (nan: not compared).
+// --device-jpeg: the enhanced frames of a step are encoded on the device (uwip_jpeg_encode_host on the pipe's context, from
+// the step's frames in the staging area) and the files are written from the returned streams: the same bytes as without it.
 // Defaults are the reference's rules (uwip_pipe_config_default); the three switches are the library's opt-in deviations.
 #include <algorithm>
 #include <cstring>
@@ -23,12 +25,13 @@ int main(int argc, char **argv)
     const Args a = parse_args(argc, argv, {"b", "batch", "c", "w", "window", "k", "p", "lookback"});
     if (a.pos.size() < 2 || a.has("h") || a.has("help")) {
         std::printf("uwpipe - bgdehaze -> histretch -> aclahe -> overlap of every frame against its predecessor\n"
-                    "usage: uwpipe [-b N] [-c LETTERS] [-w N] [--guard-s] [--min6] [--relative-threshold] [--png]\n"
+                    "usage: uwpipe [-b N] [-c LETTERS] [-w N] [--guard-s] [--min6] [--relative-threshold] [--png] [--device-jpeg]\n"
                     "              [--keyframes [-k N] [-p X] [--lookback D]] <video.avi (Motion-JPEG) | frame_list.txt> <output_prefix>\n"
                     "  -b N      frames per step (default 8)\n"
                     "  -c L      histretch letters (default RGB)\n"
                     "  -w N      bgdehaze window (default 15)\n"
                     "  --guard-s / --min6 / --relative-threshold   the library's opt-in deviations from the reference's rules (uwip.h)\n"
+                    "  --device-jpeg   encode the .jpg files on the device (same bytes; ignored with --png)\n"
                     "  --keyframes   select key frames as videostrip does (report: <prefix>videostrip_report.txt)\n"
                     "  -k N          frames of the refinement window (default 11)\n"
                     "  -p X          minOverlap (default 0.4)\n"
@@ -110,6 +113,9 @@ int main(int argc, char **argv)
         };
         const size_t nb = (n + B - 1) / B;
         std::vector<int32_t> bs(B), cl(B);
+        const bool device_jpeg = a.has("device-jpeg") && !a.has("png");
+        std::vector<uint8_t> jstreams(device_jpeg ? fbytes * B : 0);      // slot = the raw frame size
+        std::vector<int64_t> jsizes(B, -1);
         uint64_t prev_up = 0;                    // upload ticket of the step that last read h_in[(k + 1) & 1]
         if (!fill(0, h_in[0])) { rc = UWIP_ERR_INVALID; what = "reading the input"; goto fail; }
         for (size_t k = 0; k < nb; ++k) {
@@ -125,6 +131,14 @@ int main(int argc, char **argv)
             CK(uwip_pipe_last_params(pipe, bs.data(), cl.data()), "uwip_pipe_last_params");
             CK(uwip_pipe_wait(pipe, t[1]), "uwip_pipe_wait");
             CK(uwip_pipe_wait(pipe, t[2]), "uwip_pipe_wait");
+            if (device_jpeg) {
+                const uint8_t *d_frames = nullptr;
+                CK(uwip_pipe_device_results(pipe, nullptr, &d_frames, nullptr, nullptr), "uwip_pipe_device_results");
+                uwip_batch_u8 bt{};
+                bt.data = (void *)d_frames; bt.rows = rows; bt.cols = cols; bt.channels = 3; bt.frames = B;
+                bt.step = (size_t)cols * 3; bt.frame_stride = fbytes;
+                CK(uwip_jpeg_encode_host(ctx, &bt, 95, jstreams.data(), fbytes, jsizes.data()), "uwip_jpeg_encode_host");
+            }
             for (int j = 0; j < B && k * B + j < n; ++j) {
                 const size_t i = k * B + j;
                 char name[512];
@@ -132,7 +146,16 @@ int main(int argc, char **argv)
                 imgio::Image out;
                 out.rows = rows; out.cols = cols; out.channels = 3;
                 out.data.assign((uint8_t *)h_out + fbytes * j, (uint8_t *)h_out + fbytes * (j + 1));
-                if (!imgio::imwrite(name, out)) { std::printf("cannot write %s\n", name); rc = UWIP_ERR_INVALID; what = "writing"; goto fail; }
+                bool written = false;
+                if (device_jpeg && jsizes[j] > 0) {
+                    FILE *jf = std::fopen(name, "wb");
+                    written = jf && std::fwrite(jstreams.data() + fbytes * j, 1, (size_t)jsizes[j], jf) == (size_t)jsizes[j];
+                    if (jf) std::fclose(jf);
+                    if (!written) { std::printf("cannot write %s\n", name); rc = UWIP_ERR_INVALID; what = "writing"; goto fail; }
+                } else if (device_jpeg) {
+                    std::printf("\nframe %zu: its stream (%lld bytes) exceeds the slot, encoded on the host\n", i, (long long)-jsizes[j]);
+                }
+                if (!written && !imgio::imwrite(name, out)) { std::printf("cannot write %s\n", name); rc = UWIP_ERR_INVALID; what = "writing"; goto fail; }
                 // frame 0 is its own key frame (main.cpp:284-297): its row carries the self-overlap
                 report << i << "\t" << name << "\t" << ((float *)h_ratio)[j] << "\t" << bs[j] << "\t" << cl[j] << "\n";
             }

@@ -582,6 +582,28 @@ int uwip_keyframe_chain_host(const uwip_keyframe_config *kc, int n_frames, int b
  * or s = min(lookback, frames - 1) + 1 when kWindow = 0.  -1 for a bad configuration. */
 int uwip_keyframe_max_rounds(const uwip_keyframe_config *kc, int frames);
 
+/* ---- writing the frames: baseline JPEG on the device ---------------------------------------------------------------
+ * cv::imwrite(".jpg") for a batch, on the device (cli/jpeg.hpp is the host form; same bytes): baseline JFIF with the Annex K
+ * tables scaled by `quality` (clamped to 1..100; cv::imwrite's default is 95), 4:2:0 for 3-channel BGR frames, one component
+ * for 1-channel frames; any step / frame_stride / alignment, rows and cols 1..65535.
+ * uwip_jpeg_bound: the worst-case stream length of one frame, 0 for a bad geometry (host, pure, no device needed).  Derivation
+ *   from the code lengths: a block holds one DC code (the longest standard one has 11 bits, chroma category 11) with at most
+ *   11 magnitude bits and 63 AC coefficients of at most a 16-bit code and 10 magnitude bits each -- a ZRL only replaces
+ *   coefficients that are zero and an EOB only follows a shorter block -- so at most 22 + 63 * 26 = 1660 bits; the scan has
+ *   ceil(rows / m) * ceil(cols / m) MCUs of 6 blocks (m = 16, colour) or 1 block (m = 8, grey); every byte may be 0xFF and
+ *   stuffed, hence twice ceil(blocks * 1660 / 8); plus the header (623 bytes colour, 328 grey) and FF D9.
+ * uwip_jpeg_encode: asynchronous on the context's stream.  Frame f's stream starts at d_streams + f * slot_bytes and
+ *   d_sizes[f] is its length; a frame whose stream is longer than slot_bytes writes nothing and reports -(needed length) -- a
+ *   status, not an error: the other frames of the batch are unaffected.  The library's workspace for the unstuffed stream is
+ *   bounded by slot_bytes per frame as well.
+ * uwip_jpeg_encode_host: the same into host memory (frame f at h_streams + f * slot_bytes): encodes, waits, and copies only
+ *   the bytes each stream uses. */
+size_t uwip_jpeg_bound(int rows, int cols, int channels);
+int uwip_jpeg_encode(uwip_ctx *ctx, const uwip_batch_u8 *frames, int quality, uint8_t *d_streams, size_t slot_bytes,
+                     int64_t *d_sizes);
+int uwip_jpeg_encode_host(uwip_ctx *ctx, const uwip_batch_u8 *frames, int quality, uint8_t *h_streams, size_t slot_bytes,
+                          int64_t *h_sizes);
+
 #ifdef __cplusplus
 }
 #endif

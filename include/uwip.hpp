@@ -234,6 +234,34 @@ private:
     void *scratch_ = nullptr;
 };
 
+// ---- cv::imwrite(".jpg") / cv::imencode(".jpg") on the device ------------------------------------------------------
+// One baseline JPEG stream per frame of a device batch (uwip_jpeg_encode_host), byte for byte what the CLIs' host codec
+// writes.  The slot is the frame's raw size and grows to uwip_jpeg_bound for the rare batch with a frame that outgrows it.
+inline std::vector<std::vector<uint8_t>> imencode_jpeg(Context &c, const uwip_batch_u8 &frames, int quality = 95)
+{
+    const size_t F = (size_t)(frames.frames > 0 ? frames.frames : 0);
+    std::vector<std::vector<uint8_t>> out(F);
+    if (!F) return out;
+    size_t slot = (size_t)frames.rows * frames.cols * frames.channels + 1024;
+    std::vector<uint8_t> buf;
+    std::vector<int64_t> sizes(F);
+    for (int attempt = 0; attempt < 2; ++attempt) {
+        buf.resize(F * slot);
+        c.check(uwip_jpeg_encode_host(c.get(), &frames, quality, buf.data(), slot, sizes.data()));
+        bool fits = true;
+        for (int64_t s : sizes) fits = fits && s >= 0;
+        if (fits) break;
+        if (attempt) throw Error(UWIP_ERR_INVALID, "uwip_jpeg_encode_host: a stream exceeds uwip_jpeg_bound");
+        slot = uwip_jpeg_bound(frames.rows, frames.cols, frames.channels);
+    }
+    for (size_t f = 0; f < F; ++f) out[f].assign(buf.begin() + f * slot, buf.begin() + f * slot + (size_t)sizes[f]);
+    return out;
+}
+inline std::vector<std::vector<uint8_t>> imencode_jpeg(Context &c, const DeviceMat &m, int quality = 95)
+{
+    return imencode_jpeg(c, *m.batch(), quality);
+}
+
 // ---- the reference's own signatures, on a process-wide default context -------------------------------------
 // A call site of the reference switches by name alone (the `...GPU` twins of preprocessing.h:96 /
 // videostrip.hpp:84-118 are the precedent): same names, same argument order and defaults, the same globals

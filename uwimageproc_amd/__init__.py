@@ -7,5 +7,6 @@ behaviour) on top of that ABI; they hold no compute of their own and there is
 no CPU fallback.
 """
 from ._native import BatchU8, Context, Copier, PipeConfig, UwipError, batch_of, device_count, lib  # noqa: F401
+from . import jpeg  # noqa: F401
 
-__all__ = ["BatchU8", "Context", "Copier", "PipeConfig", "UwipError", "batch_of", "device_count", "lib"]
+__all__ = ["BatchU8", "Context", "Copier", "PipeConfig", "UwipError", "batch_of", "device_count", "jpeg", "lib"]

@@ -175,6 +175,9 @@ SIGNATURES = {
     "uwip_pipe_keyframes": (C.c_int, [_P, C.POINTER(KeyframeRow), C.c_int, C.POINTER(C.c_int)]),
     "uwip_keyframe_chain_host": (C.c_int, [C.POINTER(KeyframeConfig), C.c_int, C.c_int, KF_OVERLAP_FN, KF_BLUR_FN, _P,
                                            C.POINTER(KeyframeRow), C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int32)]),
+    "uwip_jpeg_bound": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+    "uwip_jpeg_encode": (C.c_int, [_P, _B, C.c_int, _P, C.c_size_t, _P]),
+    "uwip_jpeg_encode_host": (C.c_int, [_P, _B, C.c_int, _P, C.c_size_t, _P]),
 }
 
 
