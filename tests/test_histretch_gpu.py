@@ -192,3 +192,67 @@ def test_full_size_properties_1080p_4k(ctx, orc):
         exp, _ = orc.histretch(img, "RGB")
         assert np.array_equal(out, exp)
         assert out.min() == 0 and out.max() == 255
+
+
+def _hsv_pairs_image():
+    """48 x 4096 BGR: every (max, max - min) pair with each of the three channels as the maximum; the middle channel steps
+    through [min, max] and the other two swap roles from pixel to pixel, so the hue falls in all six sectors.  A second,
+    truncated pass with the roles swapped the other way fills the rest; the last 256 pixels are the grey diagonal
+    (pure black first, pure white last)."""
+    v, d = np.meshgrid(np.arange(256), np.arange(256), indexing="ij")
+    keep = d <= v
+    v, d = v[keep], d[keep]                                   # 32896 pairs, (0, 0) and (255, 0) among them
+    n = v.size
+    px = []
+    for swap in (0, 1):
+        for m in range(3):                                    # the channel that holds the maximum
+            i = np.arange(n) + m * n
+            mid = (v - d) + (i * 7) % (d + 1)
+            lo = v - d
+            a, b = [c for c in range(3) if c != m]
+            flip = ((i + swap) & 1).astype(bool)
+            p = np.empty((n, 3), np.int64)
+            p[:, m] = v
+            p[:, a] = np.where(flip, mid, lo)
+            p[:, b] = np.where(flip, lo, mid)
+            px.append(p)
+    px = np.concatenate(px)[:48 * 4096 - 256]
+    grey = np.repeat(np.arange(256)[:, None], 3, axis=1)
+    img = np.concatenate([px, grey]).astype(np.uint8).reshape(48, 4096, 3)
+    assert (img[0, 0] == 0).all() and (img[-1, -1] == 255).all() and (img[-1, -256] == 0).all()
+    return img
+
+
+def test_hsv_routes_agree_on_every_max_diff_pair(ctx, orc):
+    """The three routes through the 8-bit HSV arithmetic -- uwip_hsv_replace_v with the image's own V, uwip_cvtColor
+    BGR -> HSV -> BGR, and the in-place round trip an HSV letter of histretch leaves -- give the oracle's bytes and each
+    other's, on every (max, max - min) pair, on the 4-pixel path and (4095 columns at an odd address) the scalar one."""
+    from uwimageproc_amd import aclahe
+    full = _hsv_pairs_image()
+    for img in (full, np.ascontiguousarray(full[:, :4095])):
+        rows, cols = img.shape[:2]
+        if cols == 4096:
+            t = _dev(img)
+        else:
+            buf = torch.zeros(rows * cols * 3 + 1, dtype=torch.uint8, device="cuda")
+            t = buf[1:].view(rows, cols, 3)
+            t.copy_(torch.from_numpy(img))
+            assert t.data_ptr() % 4 == 1
+        # (a) V replaced by itself
+        v = aclahe.bgr_to_v(ctx, t)
+        assert np.array_equal(v.cpu().numpy(), orc.bgr_to_v(img))
+        a = torch.empty_like(t)
+        tb, vb, ab = batch_of(t), batch_of(v), batch_of(a)
+        torch.cuda.synchronize()
+        ctx.call("uwip_hsv_replace_v", C.byref(tb), C.byref(vb), C.byref(ab))
+        ctx.sync()
+        a = a.cpu().numpy()
+        assert np.array_equal(a, orc.hsv_replace_v(img, orc.bgr_to_v(img))), cols
+        # (b) the two conversions one after the other
+        b = pp.cvtColor(ctx, pp.cvtColor(ctx, t, 1), 1, to_bgr=True).cpu().numpy()
+        assert np.array_equal(b, orc.cvt_space(orc.cvt_space(img, 1), 1, True)), cols
+        # (c)
+        assert np.array_equal(a, b), cols
+        # (d) an HSV letter as written: the stretch is lost, the round trip stays in the image
+        pp.histretch(ctx, t, "H")
+        assert np.array_equal(t.cpu().numpy(), a), cols

@@ -1,6 +1,6 @@
 // What would a VALUE-SORTED sweep cost?  (VERDICT r3 #3 asks for the form or for a measurement that shows why not.)
 //
-// The sweep (csrc/clahe.hip, k_clahe_sweep) evaluates, per pixel and clip limit, the bilinear blend of four LUT bytes and
+// The sweep (csrc/aclahe_sweep.hip, k_clahe_sweep) evaluates, per pixel and clip limit, the bilinear blend of four LUT bytes and
 // counts the result: ~18 vector instructions + one LDS read + 0.8 LDS atomics per evaluation, 121 evaluations per pixel
 // over the five grids.  A form organised by (interpolation cell, grey level) would make the 4-tuple wave-uniform (no
 // per-lane byte conversions, no LUT gather) and would evaluate a tuple once for the whole run of limits it holds for (76

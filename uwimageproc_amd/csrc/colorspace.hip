@@ -1,5 +1,6 @@
 // 8-bit colour-space conversions behind histretch's non-BGR letters (modules/histretch/src/histretch.cpp:155-156,
-// 230-241: cvtColor(BGR2xxx) ... cvtColor(xxx2BGR) for HSV, HLS, Lab, YCrCb) for gfx950.
+// 230-241: cvtColor(BGR2xxx) ... cvtColor(xxx2BGR) for HSV, HLS, Lab, YCrCb) and aclahe's "transform back image"
+// (aclahe.cpp:216: BGR -> HSV, V := CLAHE(V), HSV -> BGR in one pass, k_hsv_replace_v) for gfx950.
 //
 // The arithmetic lives in OpenCV's imgproc/src/color.cpp, which is not in the reference tree and not in this image:
 // every conversion below is a restatement of the 8-bit code path of OpenCV 3.x from its published sources
@@ -29,7 +30,8 @@ __device__ __forceinline__ void bgr2hsv_u8(int b, int g, int r, const int *__res
     h += h < 0 ? 180 : 0;
     H = (int)(uint8_t)h; S = (int)(uint8_t)S; V = v;
 }
-__device__ __forceinline__ void hsv2bgr_u8(int H, int S, int V, int &B, int &G, int &R)
+// the inverse up to its rounding: the three channels times 255, each in [0, 255]; the caller rounds to nearest even
+__device__ __forceinline__ void hsv2bgr_f32(int H, int S, int V, float &B, float &G, float &R)
 {
     float hf = (float)H;
     const float sf = (float)S * (1.f / 255.f), vf = (float)V * (1.f / 255.f);
@@ -53,7 +55,7 @@ __device__ __forceinline__ void hsv2bgr_u8(int H, int S, int V, int &B, int &G, 
             default: ob = t2; og = t1; orr = t0; break;
         }
     }
-    B = (int)sat_u8_rne(ob * 255.f); G = (int)sat_u8_rne(og * 255.f); R = (int)sat_u8_rne(orr * 255.f);
+    B = ob * 255.f; G = og * 255.f; R = orr * 255.f;
 }
 
 // ---- HLS (RGB2HLS_b / HLS2RGB_b: the float kernels on x/255, hrange 180) ------------------------------------
@@ -226,13 +228,81 @@ __global__ __launch_bounds__(256) void k_cvt_space(const uint8_t *__restrict__ s
             a = p; b = q; c = r;
         }
         if (dir != 0) {           // inverse
-            if (SPACE == 1) hsv2bgr_u8(a, b, c, p, q, r);
+            if (SPACE == 1) {
+                float fb, fg, fr;
+                hsv2bgr_f32(a, b, c, fb, fg, fr);
+                p = (int)sat_u8_rne(fb); q = (int)sat_u8_rne(fg); r = (int)sat_u8_rne(fr);
+            }
             if (SPACE == 2) hls2bgr_u8(a, b, c, p, q, r);
             if (SPACE == 3) { if (T.rule == 0) lab2bgr_int_u8(a, b, c, T, p, q, r); else lab2bgr_u8(a, b, c, T, p, q, r); }
             if (SPACE == 4) ycc2bgr_u8(a, b, c, p, q, r);
             a = p; b = q; c = r;
         }
         d[3 * x] = (uint8_t)a; d[3 * x + 1] = (uint8_t)b; d[3 * x + 2] = (uint8_t)c;
+    }
+}
+
+// ---- "transform back image" (aclahe.cpp:216): BGR -> HSV, V := CLAHE(V), HSV -> BGR -------------------
+// one pixel: BGR -> (H, S, V) by the integer forward tables, then HSV -> BGR with the new V (vnew < 0: the pixel's own V,
+// the plain BGR -> HSV -> BGR round trip)
+__device__ __forceinline__ void hsv_replace_px(int b, int g, int r, int vnew, const int *__restrict__ sdiv,
+                                               const int *__restrict__ hdiv, uint32_t &ob8, uint32_t &og8, uint32_t &or8)
+{
+    int H, S, V;
+    bgr2hsv_u8(b, g, r, sdiv, hdiv, H, S, V);
+    float ob, og, orr;
+    hsv2bgr_f32(H, S, vnew < 0 ? V : vnew, ob, og, orr);
+    // the three values lie in [0, 255]: v_cvt_pk_u8_f32 (round to nearest even + clamp) is saturate_cast<uchar> there
+    ob8 = __builtin_amdgcn_cvt_pk_u8_f32(ob, 0, 0u);
+    og8 = __builtin_amdgcn_cvt_pk_u8_f32(og, 0, 0u);
+    or8 = __builtin_amdgcn_cvt_pk_u8_f32(orr, 0, 0u);
+}
+
+constexpr int HSV_ROWS_PER_BLOCK = 8;
+// VEC: rows are 4-byte aligned and cols % 4 == 0 -> a thread takes 4 pixels as 3 + 1 dword loads and 3 dword stores
+template <bool VEC>
+__global__ __launch_bounds__(256) void k_hsv_replace_v(const uint8_t *__restrict__ src, size_t sstep, size_t sfs,
+                                                      const uint8_t *__restrict__ vnew, size_t vstep, size_t vfs,
+                                                      uint8_t *__restrict__ dst, size_t dstep, size_t dfs, int rows,
+                                                      int cols, const int *__restrict__ sdiv_g, const int *__restrict__ hdiv_g)
+{
+    // the two division tables (2 KB) live in LDS: as global gathers they, not the pixels, set the kernel's pace
+    __shared__ int s_tab[512];
+    for (int i = threadIdx.x; i < 256; i += 256) { s_tab[i] = sdiv_g[i]; s_tab[256 + i] = hdiv_g[i]; }
+    __syncthreads();
+    const int *sdiv = s_tab, *hdiv = s_tab + 256;
+    const int f = blockIdx.z;
+    for (int y = blockIdx.y * HSV_ROWS_PER_BLOCK; y < min(rows, (int)(blockIdx.y + 1) * HSV_ROWS_PER_BLOCK); ++y) {
+    const uint8_t *s = src + (size_t)f * sfs + (size_t)y * sstep;
+    const uint8_t *vn = vnew ? vnew + (size_t)f * vfs + (size_t)y * vstep : nullptr;   // null: keep the pixel's own V
+    uint8_t *d = dst + (size_t)f * dfs + (size_t)y * dstep;
+    if (VEC) {
+        for (int x4 = blockIdx.x * 256 + threadIdx.x; x4 < cols / 4; x4 += gridDim.x * 256) {
+            const uint32_t *sp = reinterpret_cast<const uint32_t *>(s) + 3 * x4;
+            const uint32_t w[3] = {sp[0], sp[1], sp[2]};
+            const uint32_t vv = vn ? reinterpret_cast<const uint32_t *>(vn)[x4] : 0u;
+            uint32_t o[3] = {0u, 0u, 0u};
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const int k = 3 * j;
+                const int b = (w[k >> 2] >> ((k & 3) * 8)) & 255, g = (w[(k + 1) >> 2] >> (((k + 1) & 3) * 8)) & 255,
+                          r = (w[(k + 2) >> 2] >> (((k + 2) & 3) * 8)) & 255;
+                uint32_t ob, og, orr;
+                hsv_replace_px(b, g, r, vn ? (int)((vv >> (8 * j)) & 255u) : -1, sdiv, hdiv, ob, og, orr);
+                o[k >> 2] |= ob << ((k & 3) * 8);
+                o[(k + 1) >> 2] |= og << (((k + 1) & 3) * 8);
+                o[(k + 2) >> 2] |= orr << (((k + 2) & 3) * 8);
+            }
+            uint32_t *dp = reinterpret_cast<uint32_t *>(d) + 3 * x4;
+            dp[0] = o[0]; dp[1] = o[1]; dp[2] = o[2];
+        }
+    } else {
+        for (int x = blockIdx.x * 256 + threadIdx.x; x < cols; x += gridDim.x * 256) {
+            uint32_t ob, og, orr;
+            hsv_replace_px(s[3 * x], s[3 * x + 1], s[3 * x + 2], vn ? (int)vn[x] : -1, sdiv, hdiv, ob, og, orr);
+            d[3 * x] = (uint8_t)ob; d[3 * x + 1] = (uint8_t)og; d[3 * x + 2] = (uint8_t)orr;
+        }
+    }
     }
 }
 
@@ -342,7 +412,7 @@ int lab_tables(uwip_ctx *ctx, LabTabs *T)
     return UWIP_OK;
 }
 
-const int *hsv_tables2(uwip_ctx *ctx)
+const int *hsv_tables(uwip_ctx *ctx)
 {
     const void *d = uwip_table_find(ctx, "hsv.tables", nullptr);
     if (d) return (const int *)d;
@@ -352,6 +422,27 @@ const int *hsv_tables2(uwip_ctx *ctx)
         t[256 + i] = (int)std::lrint((180 << 12) / (6. * i));    // hdiv_table180
     }
     return (const int *)uwip_table_put(ctx, "hsv.tables", t.data(), t.size() * sizeof(int));
+}
+
+// k_hsv_replace_v over a batch; v_new = null: every pixel keeps its own V (src and dst may then be one image)
+int launch_hsv_replace_v(uwip_ctx *ctx, const uwip_batch_u8 *src, const uwip_batch_u8 *v_new, const uwip_batch_u8 *dst)
+{
+    const int *tabs = hsv_tables(ctx);
+    if (!tabs) return UWIP_ERR_NOMEM;
+    uwip_kscope ks(ctx, "k_hsv_replace_v");
+    auto al4 = [](const uwip_batch_u8 *b) { return !b || ((uintptr_t)b->data | b->step | b->frame_stride) % 4 == 0; };
+    const bool vec = src->cols % 4 == 0 && al4(src) && al4(v_new) && al4(dst);
+    const dim3 grid(uwip_cdiv(vec ? src->cols / 4 : src->cols, 256), (unsigned)uwip_cdiv(src->rows, HSV_ROWS_PER_BLOCK), (unsigned)src->frames);
+    const uint8_t *vn = v_new ? (const uint8_t *)v_new->data : nullptr;
+    const size_t vstep = v_new ? v_new->step : 0, vfs = v_new ? v_new->frame_stride : 0;
+    if (vec)
+        k_hsv_replace_v<true><<<grid, 256, 0, ctx->stream>>>((const uint8_t *)src->data, src->step, src->frame_stride, vn, vstep, vfs,
+                                                             (uint8_t *)dst->data, dst->step, dst->frame_stride, src->rows, src->cols, tabs, tabs + 256);
+    else
+        k_hsv_replace_v<false><<<grid, 256, 0, ctx->stream>>>((const uint8_t *)src->data, src->step, src->frame_stride, vn, vstep, vfs,
+                                                              (uint8_t *)dst->data, dst->step, dst->frame_stride, src->rows, src->cols, tabs, tabs + 256);
+    UWIP_HIP(ctx, hipGetLastError());
+    return UWIP_OK;
 }
 
 }  // namespace
@@ -368,7 +459,7 @@ int uwip_cvt_space_internal(uwip_ctx *ctx, const uwip_batch_u8 *src, const uwip_
     LabTabs T{};
     const int *hsv = nullptr;
     if (space == 3) { int rc = lab_tables(ctx, &T); if (rc) return rc; T.rule = opencv_rule; }
-    if (space == 1) { hsv = hsv_tables2(ctx); if (!hsv) return UWIP_ERR_NOMEM; }
+    if (space == 1) { hsv = hsv_tables(ctx); if (!hsv) return UWIP_ERR_NOMEM; }
     const dim3 grid(std::min(uwip_cdiv(src->cols, 256), 32u), (unsigned)src->rows, (unsigned)src->frames);
     uwip_kscope ks(ctx, "k_cvt_space");
 #define UWIP_CVT(SP) k_cvt_space<SP><<<grid, 256, 0, ctx->stream>>>((const uint8_t *)src->data, src->step, src->frame_stride, (uint8_t *)dst->data, \
@@ -394,4 +485,28 @@ UWIP_API int uwip_cvtColor_ex(uwip_ctx *ctx, const uwip_batch_u8 *src, const uwi
 UWIP_API int uwip_cvtColor(uwip_ctx *ctx, const uwip_batch_u8 *src, const uwip_batch_u8 *dst, int space, int to_bgr)
 {
     return uwip_cvtColor_ex(ctx, src, dst, space, to_bgr, 0);
+}
+
+UWIP_API int uwip_hsv_replace_v(uwip_ctx *ctx, const uwip_batch_u8 *bgr, const uwip_batch_u8 *v_new, const uwip_batch_u8 *bgr_out)
+{
+    int rc = uwip_check_batch(ctx, bgr, 3);
+    if (rc) return rc;
+    rc = uwip_check_batch(ctx, v_new, 1);
+    if (rc) return rc;
+    rc = uwip_check_batch(ctx, bgr_out, 3);
+    if (rc) return rc;
+    UWIP_REQUIRE(ctx, bgr->rows == v_new->rows && bgr->cols == v_new->cols && bgr->frames == v_new->frames &&
+                          bgr->rows == bgr_out->rows && bgr->cols == bgr_out->cols && bgr->frames == bgr_out->frames, "shape mismatch");
+    if (uwip_batch_empty(bgr)) return UWIP_OK;
+    UWIP_REQUIRE(ctx, bgr->rows <= 65535 && bgr->frames <= 65535, "too many rows/frames for one launch");
+    return launch_hsv_replace_v(ctx, bgr, v_new, bgr_out);
+}
+
+// cvtColor(BGR2HSV) followed by cvtColor(HSV2BGR), 8-bit, in place: what an HSV letter of histretch leaves in the image
+// (histretch.cpp:232-238).
+int uwip_hsv_roundtrip(uwip_ctx *ctx, const uwip_batch_u8 *img)
+{
+    if (uwip_batch_empty(img)) return UWIP_OK;
+    UWIP_REQUIRE(ctx, img->rows <= 65535 && img->frames <= 65535, "too many rows/frames for one launch");
+    return launch_hsv_replace_v(ctx, img, nullptr, img);
 }

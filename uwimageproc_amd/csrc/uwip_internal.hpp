@@ -80,7 +80,7 @@ const void *uwip_table_put(uwip_ctx *ctx, const std::string &key, const void *ho
 int uwip_prof_flush(uwip_ctx *ctx);
 // UWIP_TRACE_ALLOC=1: report an allocation's address range on stderr (attributing a GPU fault address to a buffer)
 void uwip_trace_range(const uwip_ctx *ctx, const char *kind, const char *name, const void *p, size_t bytes);
-// clahe.hip: in-place 8-bit BGR -> HSV -> BGR (an HSV letter of histretch)
+// colorspace.hip: in-place 8-bit BGR -> HSV -> BGR (an HSV letter of histretch)
 int uwip_hsv_roundtrip(uwip_ctx *ctx, const uwip_batch_u8 *img);
 // winfilter15.hip: 15x15 window max and/or min of interleaved 3-channel u8 frames -> planar [F][3][H][W]
 bool uwip_winfilter15_ok(const uint8_t *img, size_t step, size_t fs, int H, int W, int w);
@@ -191,6 +191,24 @@ static inline int uwip_check_batch(uwip_ctx *ctx, const uwip_batch_u8 *b, int ch
 static inline bool uwip_batch_empty(const uwip_batch_u8 *b)
 {
     return (size_t)b->rows * b->cols * b->frames == 0;
+}
+
+// two single-channel batches of one shape
+static inline int uwip_check_pair(uwip_ctx *ctx, const uwip_batch_u8 *src, const uwip_batch_u8 *dst)
+{
+    int rc = uwip_check_batch(ctx, src, 1);
+    if (rc) return rc;
+    rc = uwip_check_batch(ctx, dst, 1);
+    if (rc) return rc;
+    UWIP_REQUIRE(ctx, src->rows == dst->rows && src->cols == dst->cols && src->frames == dst->frames,
+                 "src/dst shape mismatch");
+    return UWIP_OK;
+}
+
+// base address, row step and (with more than one frame) frame stride are multiples of `a` bytes
+static inline bool uwip_aligned_for(const uwip_batch_u8 *b, size_t a)
+{
+    return ((uintptr_t)b->data % a == 0) && (b->step % a == 0) && (b->frames <= 1 || b->frame_stride % a == 0);
 }
 
 static inline unsigned uwip_cdiv(size_t a, size_t b) { return (unsigned)((a + b - 1) / b); }
