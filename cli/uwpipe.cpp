@@ -4,7 +4,7 @@
 //   calcOverlap of every frame against its predecessor (modules/videostrip/src/videostrip.cpp:192-289)
 // on the frames of a Motion-JPEG .avi or of a frame list, in batches through page-locked host buffers
 // (uwip_pipe_step_host: batch k + 1 is uploaded and batch k - 1 leaves while batch k's kernels run).
-//   uwpipe [-b N] [-c LETTERS] [-w N] [--guard-s] [--min6] [--relative-threshold] [--png] [--device-jpeg]
+//   uwpipe [-b N] [-c LETTERS] [-w N] [--guard-s] [--min6] [--relative-threshold] [--png] [--device-jpeg] [--device-decode]
 //          [--keyframes [-k N] [-p X] [--lookback D]] <video.avi | frame_list.txt> <output_prefix>
 // writes <prefix>NNNN.jpg (the enhanced frames) and <prefix>uwpipe_report.txt (TSV: ID, Filename, Overlap, BS, CL).
 // --keyframes: the overlap stage runs videostrip's key-frame selector (main.cpp:284-394) on the enhanced frames, on the
@@ -13,6 +13,11 @@
 // overlap against the current key frame (nan: not compared).
 // --device-jpeg: the enhanced frames of a step are encoded on the device (uwip_jpeg_encode_host on the pipe's context, from
 // the step's frames in the staging area) and the files are written from the returned streams: the same bytes as without it.
+// --device-decode (.avi, or a list of .jpg files): the compressed frames of a step are decoded on the pipe's context into a
+// device batch (uwip_jpeg_decode_host), uwip_pipe_step runs on the resident frames, and the results leave as streams
+// (--device-jpeg) or by a plain download; a frame with a negative status is decoded on the host and copied into its slot.
+// The files and both reports are the same bytes as without the flag.  The steps run one after another here (decode, step,
+// wait, results): the overlap of upload, kernels and download that uwip_pipe_step_host gives the raw-frame path is not used.
 // Defaults are the reference's rules (uwip_pipe_config_default); the three switches are the library's opt-in deviations.
 #include <algorithm>
 #include <cstring>
@@ -26,12 +31,13 @@ int main(int argc, char **argv)
     if (a.pos.size() < 2 || a.has("h") || a.has("help")) {
         std::printf("uwpipe - bgdehaze -> histretch -> aclahe -> overlap of every frame against its predecessor\n"
                     "usage: uwpipe [-b N] [-c LETTERS] [-w N] [--guard-s] [--min6] [--relative-threshold] [--png] [--device-jpeg]\n"
-                    "              [--keyframes [-k N] [-p X] [--lookback D]] <video.avi (Motion-JPEG) | frame_list.txt> <output_prefix>\n"
+                    "              [--device-decode] [--keyframes [-k N] [-p X] [--lookback D]] <video.avi (Motion-JPEG) | frame_list.txt> <output_prefix>\n"
                     "  -b N      frames per step (default 8)\n"
                     "  -c L      histretch letters (default RGB)\n"
                     "  -w N      bgdehaze window (default 15)\n"
                     "  --guard-s / --min6 / --relative-threshold   the library's opt-in deviations from the reference's rules (uwip.h)\n"
                     "  --device-jpeg   encode the .jpg files on the device (same bytes; ignored with --png)\n"
+                    "  --device-decode decode the input JPEG frames on the device (same files; a frame the device decoder leaves is decoded on the host)\n"
                     "  --keyframes   select key frames as videostrip does (report: <prefix>videostrip_report.txt)\n"
                     "  -k N          frames of the refinement window (default 11)\n"
                     "  -p X          minOverlap (default 0.4)\n"
@@ -61,6 +67,7 @@ int main(int argc, char **argv)
     uwip_ctx *ctx = nullptr;
     uwip_pipe *pipe = nullptr;
     void *h_in[2] = {nullptr, nullptr}, *h_out = nullptr, *h_ratio = nullptr;
+    void *d_in = nullptr, *d_out = nullptr, *d_ratio = nullptr;
     int rc = 0;
     const char *what = "";
 #define CK(expr, msg) do { rc = (expr); if (rc) { what = msg; goto fail; } } while (0)
@@ -91,7 +98,9 @@ int main(int argc, char **argv)
                     << (float)640 / (float)cols << "\nTarget minOverlap:\t" << kc.minOverlap << "\nWindow size:\t" << kc.kWindow << "\n";
             kreport << "***************************************\nID\tFrame\tFilename\tOverlap\tBlur\n";
         }
-        for (int s = 0; s < 2; ++s) CK(uwip_host_alloc(ctx, fbytes * B, &h_in[s]), "uwip_host_alloc");
+        // --device-decode: the compressed frames of a step, the device batches it runs on; no raw frames are uploaded
+        const bool device_decode = a.has("device-decode");
+        for (int s = 0; s < 2 && !device_decode; ++s) CK(uwip_host_alloc(ctx, fbytes * B, &h_in[s]), "uwip_host_alloc");
         CK(uwip_host_alloc(ctx, fbytes * B, &h_out), "uwip_host_alloc");
         CK(uwip_host_alloc(ctx, sizeof(float) * B, &h_ratio), "uwip_host_alloc");
 
@@ -117,23 +126,74 @@ int main(int argc, char **argv)
         std::vector<uint8_t> jstreams(device_jpeg ? fbytes * B : 0);      // slot = the raw frame size
         std::vector<int64_t> jsizes(B, -1);
         uint64_t prev_up = 0;                    // upload ticket of the step that last read h_in[(k + 1) & 1]
-        if (!fill(0, h_in[0])) { rc = UWIP_ERR_INVALID; what = "reading the input"; goto fail; }
+        std::vector<std::vector<uint8_t>> jfiles(device_decode && !is_avi ? B : 0);
+        std::vector<const uint8_t *> jptr(B);
+        std::vector<size_t> jlen(B);
+        std::vector<int32_t> jstatus(B);
+        uwip_batch_u8 bin{}, bout{};
+        if (device_decode) {
+            CK(uwip_malloc(ctx, fbytes * B, &d_in), "uwip_malloc");
+            CK(uwip_malloc(ctx, fbytes * B, &d_out), "uwip_malloc");
+            CK(uwip_malloc(ctx, sizeof(float) * B, &d_ratio), "uwip_malloc");
+            bin.rows = rows; bin.cols = cols; bin.channels = 3; bin.frames = B; bin.step = (size_t)cols * 3; bin.frame_stride = fbytes;
+            bout = bin;
+            bin.data = d_in; bout.data = d_out;
+        }
+        // decodes step k's frames into d_in: on the device, and on the host what the device decoder leaves
+        auto decode_step = [&](size_t k) -> bool {
+            for (int j = 0; j < B; ++j) {
+                const size_t i = std::min(k * B + j, n - 1);
+                if (is_avi) { jptr[j] = &video.buf[video.frames[i].first]; jlen[j] = video.frames[i].second; }
+                else {
+                    if (!imgio::read_file(frames[i], jfiles[j])) { std::printf("cannot read frame %zu\n", i); return false; }
+                    jptr[j] = jfiles[j].data(); jlen[j] = jfiles[j].size();
+                }
+            }
+            if (uwip_jpeg_decode_host(ctx, jptr.data(), jlen.data(), B, &bin, nullptr, jstatus.data())) {
+                std::printf("uwip_jpeg_decode_host: %s\n", uwip_last_error(ctx));
+                return false;
+            }
+            for (int j = 0; j < B; ++j) {
+                if (jstatus[j] == 0) continue;
+                const size_t i = std::min(k * B + j, n - 1);
+                imgio::Image im;
+                if (!read_at(i, im) || im.rows != rows || im.cols != cols || im.channels != 3) {
+                    std::printf("cannot read frame %zu (or its size differs from the first frame's)\n", i);
+                    return false;
+                }
+                if (k * B + j < n) std::printf("\nframe %zu: device decoder status %d, decoded on the host\n", i, jstatus[j]);
+                if (uwip_memcpy_h2d(ctx, (uint8_t *)d_in + fbytes * j, im.data.data(), fbytes)) return false;
+            }
+            return true;
+        };
+        if (!device_decode && !fill(0, h_in[0])) { rc = UWIP_ERR_INVALID; what = "reading the input"; goto fail; }
         for (size_t k = 0; k < nb; ++k) {
             const bool more = k + 1 < nb;
-            if (more) {
+            if (more && !device_decode) {
                 CK(uwip_pipe_wait(pipe, prev_up), "uwip_pipe_wait");           // h_in[(k + 1) & 1] has left for the device
                 if (!fill(k + 1, h_in[(k + 1) & 1])) { rc = UWIP_ERR_INVALID; what = "reading the input"; goto fail; }
             }
             if (kf && !more) CK(uwip_pipe_end_of_stream(pipe, (int)(n - k * B)), "uwip_pipe_end_of_stream");   // the padding stays out
-            uint64_t t[3];
-            CK(uwip_pipe_step_host(pipe, h_in[k & 1], h_out, (float *)h_ratio, more ? h_in[(k + 1) & 1] : nullptr, t), "uwip_pipe_step_host");
-            prev_up = t[0];
-            CK(uwip_pipe_last_params(pipe, bs.data(), cl.data()), "uwip_pipe_last_params");
-            CK(uwip_pipe_wait(pipe, t[1]), "uwip_pipe_wait");
-            CK(uwip_pipe_wait(pipe, t[2]), "uwip_pipe_wait");
+            bool have_out = true;                 // the enhanced frames are in h_out
+            if (device_decode) {
+                if (!decode_step(k)) { rc = UWIP_ERR_INVALID; what = "reading the input"; goto fail; }
+                CK(uwip_pipe_step(pipe, &bin, &bout, (float *)d_ratio, nullptr), "uwip_pipe_step");
+                CK(uwip_pipe_last_params(pipe, bs.data(), cl.data()), "uwip_pipe_last_params");
+                CK(uwip_pipe_sync(pipe), "uwip_pipe_sync");
+                CK(uwip_memcpy_d2h(ctx, h_ratio, d_ratio, sizeof(float) * B), "uwip_memcpy_d2h");
+                have_out = !device_jpeg;          // with --device-jpeg only streams leave (raw frames on demand, below)
+                if (have_out) CK(uwip_memcpy_d2h(ctx, h_out, d_out, fbytes * B), "uwip_memcpy_d2h");
+            } else {
+                uint64_t t[3];
+                CK(uwip_pipe_step_host(pipe, h_in[k & 1], h_out, (float *)h_ratio, more ? h_in[(k + 1) & 1] : nullptr, t), "uwip_pipe_step_host");
+                prev_up = t[0];
+                CK(uwip_pipe_last_params(pipe, bs.data(), cl.data()), "uwip_pipe_last_params");
+                CK(uwip_pipe_wait(pipe, t[1]), "uwip_pipe_wait");
+                CK(uwip_pipe_wait(pipe, t[2]), "uwip_pipe_wait");
+            }
             if (device_jpeg) {
-                const uint8_t *d_frames = nullptr;
-                CK(uwip_pipe_device_results(pipe, nullptr, &d_frames, nullptr, nullptr), "uwip_pipe_device_results");
+                const uint8_t *d_frames = (const uint8_t *)d_out;
+                if (!device_decode) CK(uwip_pipe_device_results(pipe, nullptr, &d_frames, nullptr, nullptr), "uwip_pipe_device_results");
                 uwip_batch_u8 bt{};
                 bt.data = (void *)d_frames; bt.rows = rows; bt.cols = cols; bt.channels = 3; bt.frames = B;
                 bt.step = (size_t)cols * 3; bt.frame_stride = fbytes;
@@ -143,9 +203,6 @@ int main(int argc, char **argv)
                 const size_t i = k * B + j;
                 char name[512];
                 std::snprintf(name, sizeof name, "%s%04zu.%s", OutputFile.c_str(), i, ext);
-                imgio::Image out;
-                out.rows = rows; out.cols = cols; out.channels = 3;
-                out.data.assign((uint8_t *)h_out + fbytes * j, (uint8_t *)h_out + fbytes * (j + 1));
                 bool written = false;
                 if (device_jpeg && jsizes[j] > 0) {
                     FILE *jf = std::fopen(name, "wb");
@@ -154,6 +211,12 @@ int main(int argc, char **argv)
                     if (!written) { std::printf("cannot write %s\n", name); rc = UWIP_ERR_INVALID; what = "writing"; goto fail; }
                 } else if (device_jpeg) {
                     std::printf("\nframe %zu: its stream (%lld bytes) exceeds the slot, encoded on the host\n", i, (long long)-jsizes[j]);
+                }
+                imgio::Image out;
+                if (!written) {
+                    if (!have_out) { CK(uwip_memcpy_d2h(ctx, h_out, d_out, fbytes * B), "uwip_memcpy_d2h"); have_out = true; }
+                    out.rows = rows; out.cols = cols; out.channels = 3;
+                    out.data.assign((uint8_t *)h_out + fbytes * j, (uint8_t *)h_out + fbytes * (j + 1));
                 }
                 if (!written && !imgio::imwrite(name, out)) { std::printf("cannot write %s\n", name); rc = UWIP_ERR_INVALID; what = "writing"; goto fail; }
                 // frame 0 is its own key frame (main.cpp:284-297): its row carries the self-overlap
@@ -184,6 +247,7 @@ fail:
         for (int s = 0; s < 2; ++s) uwip_host_free(ctx, h_in[s]);
         uwip_host_free(ctx, h_out);
         uwip_host_free(ctx, h_ratio);
+        uwip_free(ctx, d_in); uwip_free(ctx, d_out); uwip_free(ctx, d_ratio);
         uwip_ctx_destroy(ctx);
     }
     return rc ? EXIT_FAILURE : 0;

@@ -604,6 +604,46 @@ int uwip_jpeg_encode(uwip_ctx *ctx, const uwip_batch_u8 *frames, int quality, ui
 int uwip_jpeg_encode_host(uwip_ctx *ctx, const uwip_batch_u8 *frames, int quality, uint8_t *h_streams, size_t slot_bytes,
                           int64_t *h_sizes);
 
+/* ---- reading the frames: baseline JPEG on the device ---------------------------------------------------------------
+ * cv::imread / cv::imdecode for a batch, on the device (jpeg::decode of cli/jpeg.hpp is the host form; where the status is 0,
+ * the same pixels byte for byte, the host decoder's rules for a truncated segment included: bits past the end, or past a
+ * marker that is no RSTn, read as zeros).  Baseline (SOF0 / SOF1, 8 bit, Huffman), one interleaved scan, 1 or 3 components,
+ * sampling factors 1..2, restart intervals; Motion-JPEG frames without DHT use the Annex K tables.
+ * uwip_jpeg_info: the header parse alone (host, pure, no device needed): rows, cols and the component count (1 or 3) of a
+ *   stream jpeg::decode would start to decode; UWIP_ERR_UNSUPPORTED where its parse fails (not 8 bit, progressive and the
+ *   other non-baseline SOFs, more than one SOF, a component count other than 1 or 3, sampling factors outside 1..2, short
+ *   segments, no scan).
+ * uwip_jpeg_decode: parses the n streams on the host, copies their entropy-coded segments through page-locked staging owned
+ *   by the library to the device on the context's stream, queues the kernels and returns without waiting (reuse of the
+ *   staging buffer waits, polling an event, for the previous call's upload only).  `out` is a device batch of n frames with 3
+ *   channels (BGR; a one-component stream is replicated) or 1 channel (one-component streams only); any step, frame_stride
+ *   and alignment.  d_status[f] (device) is 0 or one of the codes below -- a status, not an error: the other frames are
+ *   complete, and the pixels of a frame with a negative status are unspecified but stay inside its slot.  A caller decodes
+ *   such a frame on the host and uploads it into its slot.
+ *     UWIP_JPEG_BAD_STREAM     jpeg::decode returns false: parse errors, an undecodable Huffman code, a DC category above 11,
+ *                              a DC predictor outside 16 bits, a run past coefficient 63
+ *     UWIP_JPEG_SIZE_MISMATCH  the SOF size is not out->rows x out->cols, or a colour stream goes into a 1-channel batch
+ *     UWIP_JPEG_HOST_ONLY      the host decoder reads the stream, the device does not: a component sampled 1x2 against the
+ *                              largest factors, or an entropy-coded segment whose markers before the first non-RST marker
+ *                              are not exactly ceil(MCUs / Ri) - 1 RSTn in cyclic order
+ *   opts (NULL: the defaults): sync_rounds is the number of synchronisation rounds of the entropy decoder, -1 the
+ *   library's choice, 0 none (one lane per restart interval decodes serially); d_unsettled, when not NULL, receives two
+ *   64-bit counts on the device: subsequences still unsettled after the rounds, subsequences in all.
+ * uwip_jpeg_decode_host: the same, waits, and returns the status array in host memory. */
+#define UWIP_JPEG_BAD_STREAM    (-1)
+#define UWIP_JPEG_SIZE_MISMATCH (-2)
+#define UWIP_JPEG_HOST_ONLY     (-3)
+typedef struct uwip_jpeg_decode_opts {
+    int32_t sync_rounds;
+    int32_t reserved;             /* 0 */
+    uint64_t *d_unsettled;
+} uwip_jpeg_decode_opts;
+int uwip_jpeg_info(const uint8_t *buf, size_t len, int32_t *rows, int32_t *cols, int32_t *channels);
+int uwip_jpeg_decode(uwip_ctx *ctx, const uint8_t *const *h_streams, const size_t *h_sizes, int n, const uwip_batch_u8 *out,
+                     const uwip_jpeg_decode_opts *opts, int32_t *d_status);
+int uwip_jpeg_decode_host(uwip_ctx *ctx, const uint8_t *const *h_streams, const size_t *h_sizes, int n, const uwip_batch_u8 *out,
+                          const uwip_jpeg_decode_opts *opts, int32_t *h_status);
+
 #ifdef __cplusplus
 }
 #endif

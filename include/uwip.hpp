@@ -262,6 +262,30 @@ inline std::vector<std::vector<uint8_t>> imencode_jpeg(Context &c, const DeviceM
     return imencode_jpeg(c, *m.batch(), quality);
 }
 
+// ---- cv::imdecode of JPEG streams on the device -------------------------------------------------------------------------
+// One frame of the device batch `out` per baseline JPEG / Motion-JPEG stream (uwip_jpeg_decode_host): where the returned
+// status is 0, the pixels of the CLIs' host decoder byte for byte; a negative status (UWIP_JPEG_BAD_STREAM / _SIZE_MISMATCH /
+// _HOST_ONLY) leaves the other frames complete -- decode such a frame on the host and upload it into its slot.
+inline std::vector<int32_t> imdecode_jpeg(Context &c, const std::vector<const uint8_t *> &streams, const std::vector<size_t> &sizes,
+                                          const uwip_batch_u8 &out, int sync_rounds = -1)
+{
+    if (streams.size() != sizes.size()) throw Error(UWIP_ERR_INVALID, "imdecode_jpeg: one size per stream");
+    std::vector<int32_t> status(streams.size(), 0);
+    if (streams.empty()) return status;
+    uwip_jpeg_decode_opts opts{};
+    opts.sync_rounds = sync_rounds;
+    c.check(uwip_jpeg_decode_host(c.get(), streams.data(), sizes.data(), (int)streams.size(), &out, &opts, status.data()));
+    return status;
+}
+inline std::vector<int32_t> imdecode_jpeg(Context &c, const std::vector<std::vector<uint8_t>> &streams, const uwip_batch_u8 &out,
+                                          int sync_rounds = -1)
+{
+    std::vector<const uint8_t *> p;
+    std::vector<size_t> n;
+    for (const auto &s : streams) { p.push_back(s.data()); n.push_back(s.size()); }
+    return imdecode_jpeg(c, p, n, out, sync_rounds);
+}
+
 // ---- the reference's own signatures, on a process-wide default context -------------------------------------
 // A call site of the reference switches by name alone (the `...GPU` twins of preprocessing.h:96 /
 // videostrip.hpp:84-118 are the precedent): same names, same argument order and defaults, the same globals

@@ -1,0 +1,139 @@
+// The kernels of uwimageproc_amd/csrc/jpeg_decode.hip executed on the host, thread for thread: one std::thread per GPU thread
+// and a barrier for __syncthreads in the kernels that synchronise, a plain loop over the threads in those that do not,
+// workgroups one after another, against jpeg::decode (cli/jpeg.hpp) into a strided, misaligned batch.  It checks the kernels'
+// logic (and, under the sanitizers, every index they form) where there is no device; the GPU tests check the compiled kernels.
+// tests/test_jpeg_decode_emulated.py cuts the kernels out of the .hip file into kernels_dec.inc (everything inside its
+// anonymous namespace), builds this file with the host compiler and gives it the streams:
+//   emu <list file>      one line per case: <path> <sync_rounds> <channels of the batch>
+// and prints per case: <path> <sync_rounds> status <s> host <0|1> equal <0|1> clean <0|1> unsettled <u> of <n>
+#include <algorithm>
+#include <atomic>
+#include <barrier>
+#include <cstdint>
+#include <cstdio>
+#include <cstring>
+#include <fstream>
+#include <functional>
+#include <sstream>
+#include <thread>
+#include <vector>
+#include "uwip.h"
+#include "jpeg.hpp"
+#include "jpeg_parse.hpp"
+struct d3 { unsigned x = 1, y = 1, z = 1; };
+static thread_local d3 threadIdx, blockIdx, blockDim;
+static std::barrier<> *g_bar;
+#define __global__ static
+#define __device__ static
+#define __forceinline__ inline
+#define __shared__ static
+#define __launch_bounds__(x)
+#define __restrict__
+static void __syncthreads() { g_bar->arrive_and_wait(); }
+static uint32_t atomicOr(uint32_t *p, uint32_t v) { return __atomic_fetch_or(p, v, __ATOMIC_SEQ_CST); }
+static uint32_t atomicMin(uint32_t *p, uint32_t v)
+{
+    uint32_t o = __atomic_load_n(p, __ATOMIC_SEQ_CST);
+    while (v < o && !__atomic_compare_exchange_n(p, &o, v, false, __ATOMIC_SEQ_CST, __ATOMIC_SEQ_CST)) {}
+    return o;
+}
+static uint32_t atomicAdd(uint32_t *p, uint32_t v) { return __atomic_fetch_add(p, v, __ATOMIC_SEQ_CST); }
+static unsigned long long atomicAdd(unsigned long long *p, unsigned long long v) { return __atomic_fetch_add(p, v, __ATOMIC_SEQ_CST); }
+using std::min; using std::max;
+static unsigned uwip_cdiv(size_t a, size_t b) { return (unsigned)((a + b - 1) / b); }
+static uint32_t g_vals[256];
+static uint32_t block256_incl_scan_u32(uint32_t v, uint32_t *)
+{
+    __syncthreads(); g_vals[threadIdx.x] = v; __syncthreads();
+    uint32_t s = 0; for (unsigned i = 0; i <= threadIdx.x; ++i) s += g_vals[i];
+    __syncthreads(); return s;
+}
+#include "kernels_dec.inc"
+template <class F> static void launch(unsigned gx, unsigned gy, unsigned bs, bool sync, F f)
+{
+    for (unsigned by = 0; by < gy; ++by) for (unsigned bx = 0; bx < gx; ++bx) {
+        if (!sync) {
+            for (unsigned t = 0; t < bs; ++t) { threadIdx.x = t; blockIdx.x = bx; blockIdx.y = by; blockDim.x = bs; f(); }
+            continue;
+        }
+        std::barrier<> bar(bs); g_bar = &bar;
+        std::vector<std::thread> th;
+        for (unsigned t = 0; t < bs; ++t) th.emplace_back([=, &bar] { g_bar = &bar; threadIdx.x = t; blockIdx.x = bx; blockIdx.y = by; blockDim.x = bs; f(); });
+        for (auto &t : th) t.join();
+    }
+}
+// uwip_jpeg_decode's host side for one frame, the kernels on host threads
+static int decode(const std::vector<uint8_t> &stream, int sync_rounds, uint8_t *out, size_t step, size_t fs, int rows, int cols, int channels,
+                  int32_t *status, unsigned long long *stats)
+{
+    const int n = 1, rounds = rounds_of(sync_rounds);
+    std::vector<DecFrame> fr(n);
+    size_t seg = 0;
+    std::memset(&fr[0], 0, sizeof(DecFrame));
+    int r = 0, c = 0, ch = 0;
+    fr[0].status = uwip_jpeg::parse(stream.data(), stream.size(), &r, &c, &ch, &fr[0], &seg);
+    if (fr[0].status == 0 && (r != rows || c != cols || (ch == 3 && channels == 1))) fr[0].status = UWIP_JPEG_SIZE_MISMATCH;
+    if (fr[0].status == 0) fr[0].seg_len = (uint32_t)(stream.size() - seg);
+    DecPlan pl;
+    plan_layout(fr.data(), n, pl);
+    // exact sizes, so that the address sanitizer sees an index one past any of them
+    std::vector<uint8_t> src(pl.src_bytes, 0xEE), ubuf(pl.ubuf_bytes + 16, 0xEE), planes(pl.plane_bytes + 16, 0xEE);
+    if (fr[0].status == 0 && fr[0].seg_len) std::memcpy(src.data() + fr[0].seg_off, stream.data() + seg, fr[0].seg_len);
+    const size_t ni = pl.nintv + 1, ns = pl.nsub + 1;
+    std::vector<uint64_t> e0(ns, 0x5555), e1(ns, 0x5555), en(ns, 0x5555);
+    std::vector<uint32_t> cnt(ns, 77), sblk(ns, 77), sint(ns, 77), istart(ni, 77), isub(ni, 77), ifirst(ni, 0xFFFFFFFFu);
+    std::vector<int16_t> coef((pl.nblk + 1) * 64, 0);
+    int32_t err = 0;
+    stats[0] = stats[1] = 0;
+    DecBufs B;
+    B.fr = fr.data(); B.src = src.data(); B.ubuf = ubuf.data();
+    B.exit0 = e0.data(); B.exit1 = e1.data(); B.entry = en.data(); B.stats = stats;
+    B.cnt = cnt.data(); B.sblk = sblk.data(); B.sint = sint.data(); B.istart = istart.data(); B.isub = isub.data(); B.ifirst = ifirst.data();
+    B.coef = coef.data(); B.planes = planes.data(); B.status = status; B.err = &err;
+    const unsigned gsub = uwip_cdiv(pl.max_sub ? pl.max_sub : 1, 256), gint = uwip_cdiv(pl.max_int ? pl.max_int : 1, 64);
+    const unsigned gblk = uwip_cdiv(pl.max_blk ? pl.max_blk : 1, 64), gpix = uwip_cdiv((size_t)rows * cols, 256);
+    launch(n, 1, 256, true, [=] { k_jpd_unstuff(B); });
+    for (int rr = 0; rr <= rounds; ++rr) launch(gsub, n, 256, true, [=] { k_jpd_round(B, rr); });
+    launch(gsub, n, 256, true, [=] { k_jpd_check(B, rounds); });
+    launch(gint, n, 64, true, [=] { k_jpd_cleanup(B, rounds); });
+    launch(n, 1, 256, true, [=] { k_jpd_blkscan(B); });
+    launch(gsub, n, 256, true, [=] { k_jpd_write(B, rounds); });
+    launch(3, n, 256, true, [=] { k_jpd_dc(B); });
+    launch(gblk, n, 64, false, [=] { k_jpd_idct(B); });
+    launch(gpix, n, 256, false, [=] { k_jpd_color(B, out, step, fs, rows, cols, channels); });
+    return 0;
+}
+int main(int argc, char **argv)
+{
+    if (argc < 2) return 2;
+    std::ifstream list(argv[1]);
+    std::string line;
+    while (std::getline(list, line)) {
+        std::istringstream is(line);
+        std::string path; int rounds = -1, channels = 3;
+        if (!(is >> path >> rounds >> channels)) continue;
+        std::ifstream f(path, std::ios::binary);
+        std::vector<uint8_t> s((std::istreambuf_iterator<char>(f)), std::istreambuf_iterator<char>());
+        int rows = 0, cols = 0, ch = 0;
+        std::vector<uint8_t> host;
+        const bool host_ok = jpeg::decode(s.data(), s.size(), rows, cols, ch, host, channels == 3);
+        int32_t ir = 0, ic = 0, ich = 0;
+        const int info = uwip_jpeg::parse(s.data(), s.size(), &ir, &ic, &ich, nullptr, nullptr);
+        if (!host_ok) { rows = info == 0 ? ir : 8; cols = info == 0 ? ic : 8; }
+        const size_t step = (size_t)cols * channels + 5, fs = step * rows + 77;
+        std::vector<uint8_t> buf(fs + 3, 0xA5);
+        uint8_t *out = buf.data() + 3;
+        int32_t status = 99;
+        unsigned long long stats[2];
+        decode(s, rounds, out, step, fs, rows, cols, channels, &status, stats);
+        bool equal = host_ok && status == 0, clean = true;
+        for (int y = 0; y < rows && equal; ++y) equal = !std::memcmp(out + y * step, host.data() + (size_t)y * cols * channels, (size_t)cols * channels);
+        for (size_t i = 0; i < buf.size(); ++i) {
+            const size_t o = i < 3 ? SIZE_MAX : i - 3;
+            const bool inside = o != SIZE_MAX && o / step < (size_t)rows && o % step < (size_t)cols * channels;
+            if (!inside && buf[i] != 0xA5) clean = false;
+        }
+        std::printf("%s %d status %d host %d equal %d clean %d unsettled %llu of %llu\n", path.c_str(), rounds, status, (int)host_ok, (int)equal, (int)clean, stats[0], stats[1]);
+    }
+    return 0;
+}

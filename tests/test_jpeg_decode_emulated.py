@@ -1,0 +1,185 @@
+"""CPU: the kernels of csrc/jpeg_decode.hip run on host threads (tests/jpeg_decode_emulated.cpp, built with the address and
+undefined-behaviour sanitizers) and must return the host decoder's pixels (jpeg::decode, cli/jpeg.hpp) for every stream it
+decodes, BAD_STREAM where it does not, and write nothing outside the frame."""
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+import _jpeg_streams as js
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+@pytest.fixture(scope="module")
+def emu(tmp_path_factory):
+    d = tmp_path_factory.mktemp("jpd_emu")
+    src = open(os.path.join(ROOT, "uwimageproc_amd", "csrc", "jpeg_decode.hip")).read()
+    a, end = src.index("namespace {"), "}  // namespace\n"
+    b = src.index(end)
+    open(str(d / "kernels_dec.inc"), "w").write(src[a:b + len(end)])
+    exe = str(d / "emu")
+    subprocess.run(["g++", "-std=c++20", "-O1", "-pthread", "-w", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
+                    "-I", str(d), "-I", os.path.join(ROOT, "include"), "-I", os.path.join(ROOT, "cli"),
+                    "-I", os.path.join(ROOT, "uwimageproc_amd", "csrc"), os.path.join(ROOT, "tests", "jpeg_decode_emulated.cpp"),
+                    "-o", exe], check=True, timeout=600)
+
+    def run(cases):
+        """cases: [(name, stream, channels, rounds)] -> {(name, rounds): dict of the printed fields}"""
+        lines = []
+        for name, stream, ch, rounds in cases:
+            p = str(d / (name + ".jpg"))
+            open(p, "wb").write(stream)
+            lines.append(f"{p} {rounds} {ch}")
+        lst = str(d / "list.txt")
+        open(lst, "w").write("\n".join(lines) + "\n")
+        r = subprocess.run([exe, lst], capture_output=True, text=True, timeout=1500)
+        assert r.returncode == 0, (r.stdout + r.stderr)[-3000:]
+        out = {}
+        for ln in r.stdout.splitlines():
+            w = ln.split()
+            out[(os.path.basename(w[0])[:-4], int(w[1]))] = {"status": int(w[3]), "host": int(w[5]), "equal": int(w[7]), "clean": int(w[9]),
+                                                            "unsettled": int(w[11]), "lanes": int(w[13])}
+        assert len(out) == len(cases), r.stdout[-3000:]
+        return out
+    return run
+
+
+def test_every_kind_at_every_round_count(emu):
+    cases = [(n, s, ch, r) for n, s, ch in js.kinds() for r in (0, 1, -1)]
+    noise = js.content(135, 243, "noise")
+    for sub in (0, 2):
+        s = js.pil_stream(noise, 100, sub)
+        assert b"\xff\x00" in s[js.segment_start(s):]
+        cases += [(f"noise_s{sub}", s, 3, r) for r in (0, 1, -1)]
+    g = js.pil_stream(np.ascontiguousarray(noise[..., 0]), 100)
+    cases += [("noise_grey1", g, 1, r) for r in (0, -1)]
+    std = js.pil_stream(js.content(61, 83), 90, 2)
+    assert js.strip_dht(std) != std
+    cases += [("nodht", js.strip_dht(std), 3, r) for r in (0, -1)]
+    res = emu(cases)
+    bad = {k: v for k, v in res.items() if not (v["status"] == 0 and v["host"] and v["equal"] and v["clean"])}
+    assert not bad, bad
+    # the noise frame spans many subsequences, and the sync rounds settle them
+    assert res[("noise_s0", -1)]["lanes"] > 100
+    assert res[("noise_s0", 0)]["unsettled"] > res[("noise_s0", -1)]["unsettled"]
+
+
+def test_truncated_streams_follow_the_host_decoder(emu):
+    cases, restart = [], set()
+    for sub in (0, 1, 2, "grey"):
+        for form in ("plain", "rstrows"):
+            img = js.content(61, 83)
+            s = js.pil_stream(np.ascontiguousarray(img[..., 1]) if sub == "grey" else img, 95, 0 if sub == "grey" else sub, **js.FORMS[form])
+            a = js.segment_start(s)
+            for i, cut in enumerate((a, a + 1, a + (len(s) - a) // 3, a + (len(s) - a) // 2 + 1, len(s) - 3, len(s) - 2, len(s) - 1)):
+                name = f"trunc_s{sub}_{form}_{i}"
+                if form != "plain":
+                    restart.add(name)
+                cases += [(name, s[:cut], 3, r) for r in (0, -1)]
+    # the other forms and sizes, at three cut points each
+    for H, W in ((61, 83), (17, 33), (16, 16), (135, 243)):
+        for sub in (0, 1, 2, "grey"):
+            for form in (("optimize", "rstblocks") if (H, W) == (61, 83) else tuple(js.FORMS)):
+                if (H, W) == (135, 243) and (sub in (1, "grey") or form in ("optimize", "rstblocks")):
+                    continue
+                img = js.content(H, W)
+                s = js.pil_stream(np.ascontiguousarray(img[..., 1]) if sub == "grey" else img, 95, 0 if sub == "grey" else sub, **js.FORMS[form])
+                a = js.segment_start(s)
+                for i, cut in enumerate((a + 2, a + (len(s) - a) // 2, len(s) - 2)):
+                    name = f"trunc_{H}x{W}_s{sub}_{form}_{i}"
+                    if form.startswith("rst"):
+                        restart.add(name)
+                    cases.append((name, s[:cut], 3, -1))
+    res = emu(cases)
+    for (name, r), v in res.items():
+        assert v["clean"], (name, r, v)
+        if v["status"] == 0:
+            assert v["host"] and v["equal"], (name, r, v)
+        elif v["status"] == -3:
+            assert name in restart, (name, r, v)          # fewer RSTn than intervals: the host decoder's business
+        else:
+            assert v["status"] == -1 and not v["host"], (name, r, v)
+    # a stream without restart markers is decoded on the device wherever it is cut
+    assert all(v["status"] == 0 for (name, r), v in res.items() if name not in restart)
+
+
+def test_noise_in_the_segment_is_bad_stream_or_the_host_pixels(emu):
+    cases = []
+    for sub in (0, 2):
+        s = js.pil_stream(js.content(61, 83), 95, sub, optimize=True)
+        a = js.segment_start(s)
+        for seed in range(6):
+            rng = np.random.default_rng(seed)
+            t = bytearray(s)
+            at = int(rng.integers(a, len(s) - 40))
+            noise = rng.integers(0, 255, size=32, dtype=np.uint8)          # no 0xFF: the segment keeps its marker layout
+            t[at:at + 32] = noise.tobytes()
+            cases += [(f"noisy_s{sub}_{seed}", bytes(t), 3, r) for r in (0, 1, -1)]
+    res = emu(cases)
+    for (name, r), v in res.items():
+        assert v["clean"], (name, r, v)
+        if v["host"]:
+            assert v["status"] == 0 and v["equal"], (name, r, v)
+        else:
+            assert v["status"] == -1, (name, r, v)
+
+
+def test_quantisers_of_255_take_the_64_bit_path(emu):
+    s = bytearray(js.pil_stream(js.content(17, 33, "noise"), 100, 0))
+    pos, n = 2, 0
+    while s[pos + 1] != 0xDA:
+        L = (s[pos + 2] << 8) | s[pos + 3]
+        if s[pos + 1] == 0xDB:
+            q = pos + 4
+            while q < pos + 2 + L:
+                assert s[q] >> 4 == 0
+                s[q + 1:q + 65] = b"\xff" * 64
+                q += 65
+                n += 1
+        pos += 2 + L
+    assert n == 2
+    res = emu([("q255", bytes(s), 3, r) for r in (0, -1)])
+    for k, v in res.items():
+        assert v["status"] == 0 and v["host"] and v["equal"] and v["clean"], (k, v)
+
+
+def test_host_only_streams_are_reported_not_decoded(emu):
+    img = js.content(61, 83)
+    rst = js.pil_stream(img, 95, 2, restart_marker_rows=1)
+    s422 = js.pil_stream(img, 95, 1)
+    extra = rst[:-2] + b"\xff\xd7" + rst[-2:]                     # one RSTn more than intervals, before EOI
+    cases = [("ho_misplaced", js.misplaced_rst(rst), 3, -1), ("ho_1x2", js.sampled_1x2(s422), 3, -1), ("ho_extra", extra, 3, -1),
+             ("ho_ref", rst, 3, -1)]
+    res = emu(cases)
+    assert res[("ho_ref", -1)]["status"] == 0 and res[("ho_ref", -1)]["equal"]
+    for name in ("ho_misplaced", "ho_1x2", "ho_extra"):
+        v = res[(name, -1)]
+        assert v["status"] == -3 and v["host"] and v["clean"], (name, v)
+
+
+def test_mutated_headers_are_accepted_or_rejected_as_the_host_decoder_does(emu):
+    """jpeg_parse.hpp restates the header walk of jpeg::decode: with one header byte changed the two must still agree on
+    whether the stream decodes, and on the pixels where it does."""
+    s = js.pil_stream(js.content(17, 33), 90, 2, restart_marker_blocks=3)
+    a = js.segment_start(s)
+    rng = np.random.default_rng(5)
+    marks = [i for i in range(2, a - 1) if s[i] == 0xFF and s[i + 1] not in (0, 0xFF)]
+    at = sorted(set(int(v) for v in rng.integers(2, a, size=6)) | {m + d for m in marks for d in (1, 2, 3)} |
+                {s.index(b"\xff\xc0") + d for d in range(4, 19)})
+    cases = [(f"mut_{i}_{val}", s[:i] + bytes([val]) + s[i + 1:], 3, -1)
+             for i in at if i < a for val in sorted({0xFF, s[i] ^ 0x01, s[i] ^ 0x10} - {s[i]})]
+    res = emu(cases)
+    assert len(res) > 100
+    n_bad = 0
+    for (name, r), v in res.items():
+        assert v["clean"], (name, v)
+        if v["status"] == -1:
+            assert not v["host"], (name, v)
+            n_bad += 1
+        elif v["status"] == 0:
+            assert v["host"] and v["equal"], (name, v)
+        else:
+            assert v["status"] in (-2, -3) and v["host"], (name, v)      # a size the batch does not have / host only: both decodable
+    assert n_bad > 20

@@ -59,6 +59,8 @@ struct uwip_ctx {
     // blocking-sync events included: eight sub-batch threads of a rank burned eight cores, measured host_cpu_s_per_step
     // 1.59 s per 0.177 s step); UWIP_CTX_SPIN_WAIT keeps the spinning wait
     hipEvent_t wait_ev = nullptr;
+    // uwip_jpeg_decode: recorded behind the upload out of the page-locked staging buffer, polled before the next call refills it
+    hipEvent_t jpd_ev = nullptr;
     bool spin_wait = false;
 
     int fail(int code, const char *what, const char *detail = nullptr)
