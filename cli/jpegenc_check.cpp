@@ -5,34 +5,9 @@
 // host one is written before the device is touched).
 // --time N: both encoders on N copies of the image (the frames already in device memory for the device one, the host one on
 // one thread), milliseconds for each, then the device kernels' split from uwip_prof_* (ms per N frames per kernel).
-// At start it asserts that the library's tables (csrc/jpeg_tables.hpp) are the host codec's.
+// The two share their tables, header writer and DCT pass (csrc/jpeg_tables.hpp, jpeg_core.hpp); everything else is compared here.
 #include <cstdlib>
 #include "cliutil.hpp"
-#include "../uwimageproc_amd/csrc/jpeg_tables.hpp"
-
-static bool tables_agree()
-{
-    namespace L = uwip_jpeg;
-    namespace H = jpeg;
-    bool ok = sizeof L::ZIGZAG == sizeof H::ZIGZAG && !std::memcmp(L::ZIGZAG, H::ZIGZAG, sizeof H::ZIGZAG);
-#define SAME(t) ok = ok && sizeof L::t == sizeof H::t && !std::memcmp(L::t, H::t, sizeof H::t)
-    SAME(STD_LUM_Q); SAME(STD_CHR_Q); SAME(DC_LUM_BITS); SAME(DC_CHR_BITS); SAME(DC_VALS);
-    SAME(AC_LUM_BITS); SAME(AC_LUM_VALS); SAME(AC_CHR_BITS); SAME(AC_CHR_VALS);
-#undef SAME
-    // and the codes built from them are the ones jpeg::HuffTable::build assigns
-    H::HuffTable dc[2], ac[2];
-    H::default_tables(dc, ac);
-    const uint8_t *bits[4] = {L::DC_LUM_BITS, L::DC_CHR_BITS, L::AC_LUM_BITS, L::AC_CHR_BITS};
-    const uint8_t *vals[4] = {L::DC_VALS, L::DC_VALS, L::AC_LUM_VALS, L::AC_CHR_VALS};
-    const H::HuffTable *ht[4] = {&dc[0], &dc[1], &ac[0], &ac[1]};
-    for (int t = 0; t < 4; ++t) {
-        uint32_t c[256];
-        L::build_codes(bits[t], vals[t], c);
-        for (int s = 0; s < 256; ++s)
-            ok = ok && (c[s] >> 16) == ht[t]->esize[s] && (!ht[t]->esize[s] || (c[s] & 0xffffu) == ht[t]->ecode[s]);
-    }
-    return ok;
-}
 
 static bool dump(const std::string &path, const uint8_t *p, size_t n)
 {
@@ -47,7 +22,6 @@ int main(int argc, char **argv)
 {
     const Args a = parse_args(argc, argv, {"time"});
     if (a.pos.size() < 2) { std::printf("usage: jpegenc_check <image> <quality> [grey] [--out=FILE] [--host-out=FILE] [--time N]\n"); return 2; }
-    if (!tables_agree()) { std::printf("csrc/jpeg_tables.hpp differs from the tables of cli/jpeg.hpp\n"); return 3; }
     const bool grey = a.pos.size() > 2 && a.pos[2] == "grey";
     const int quality = std::atoi(a.pos[1].c_str());
     imgio::Image im;

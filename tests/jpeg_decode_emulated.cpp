@@ -6,62 +6,15 @@
 // anonymous namespace), builds this file with the host compiler and gives it the streams:
 //   emu <list file>      one line per case: <path> <sync_rounds> <channels of the batch>
 // and prints per case: <path> <sync_rounds> status <s> host <0|1> equal <0|1> clean <0|1> unsettled <u> of <n>
-#include <algorithm>
-#include <atomic>
-#include <barrier>
-#include <cstdint>
 #include <cstdio>
 #include <cstring>
 #include <fstream>
-#include <functional>
 #include <sstream>
-#include <thread>
-#include <vector>
 #include "uwip.h"
 #include "jpeg.hpp"
 #include "jpeg_parse.hpp"
-struct d3 { unsigned x = 1, y = 1, z = 1; };
-static thread_local d3 threadIdx, blockIdx, blockDim;
-static std::barrier<> *g_bar;
-#define __global__ static
-#define __device__ static
-#define __forceinline__ inline
-#define __shared__ static
-#define __launch_bounds__(x)
-#define __restrict__
-static void __syncthreads() { g_bar->arrive_and_wait(); }
-static uint32_t atomicOr(uint32_t *p, uint32_t v) { return __atomic_fetch_or(p, v, __ATOMIC_SEQ_CST); }
-static uint32_t atomicMin(uint32_t *p, uint32_t v)
-{
-    uint32_t o = __atomic_load_n(p, __ATOMIC_SEQ_CST);
-    while (v < o && !__atomic_compare_exchange_n(p, &o, v, false, __ATOMIC_SEQ_CST, __ATOMIC_SEQ_CST)) {}
-    return o;
-}
-static uint32_t atomicAdd(uint32_t *p, uint32_t v) { return __atomic_fetch_add(p, v, __ATOMIC_SEQ_CST); }
-static unsigned long long atomicAdd(unsigned long long *p, unsigned long long v) { return __atomic_fetch_add(p, v, __ATOMIC_SEQ_CST); }
-using std::min; using std::max;
-static unsigned uwip_cdiv(size_t a, size_t b) { return (unsigned)((a + b - 1) / b); }
-static uint32_t g_vals[256];
-static uint32_t block256_incl_scan_u32(uint32_t v, uint32_t *)
-{
-    __syncthreads(); g_vals[threadIdx.x] = v; __syncthreads();
-    uint32_t s = 0; for (unsigned i = 0; i <= threadIdx.x; ++i) s += g_vals[i];
-    __syncthreads(); return s;
-}
+#include "hip_on_host.hpp"
 #include "kernels_dec.inc"
-template <class F> static void launch(unsigned gx, unsigned gy, unsigned bs, bool sync, F f)
-{
-    for (unsigned by = 0; by < gy; ++by) for (unsigned bx = 0; bx < gx; ++bx) {
-        if (!sync) {
-            for (unsigned t = 0; t < bs; ++t) { threadIdx.x = t; blockIdx.x = bx; blockIdx.y = by; blockDim.x = bs; f(); }
-            continue;
-        }
-        std::barrier<> bar(bs); g_bar = &bar;
-        std::vector<std::thread> th;
-        for (unsigned t = 0; t < bs; ++t) th.emplace_back([=, &bar] { g_bar = &bar; threadIdx.x = t; blockIdx.x = bx; blockIdx.y = by; blockDim.x = bs; f(); });
-        for (auto &t : th) t.join();
-    }
-}
 // uwip_jpeg_decode's host side for one frame, the kernels on host threads
 static int decode(const std::vector<uint8_t> &stream, int sync_rounds, uint8_t *out, size_t step, size_t fs, int rows, int cols, int channels,
                   int32_t *status, unsigned long long *stats)

@@ -2,62 +2,17 @@
 // barrier for __syncthreads, workgroups one after another, against jpeg::encode (cli/jpeg.hpp) on strided, misaligned batches,
 // with slots that fit, are one byte short, or are far too small.  It checks the kernels' logic where there is no device; the
 // GPU tests check the compiled kernels.  tests/test_jpeg_encode_emulated.py cuts the kernels out of the .hip file into
-// kernels.inc (everything inside its anonymous namespace) and builds this file with the host compiler.
-#include <algorithm>
-#include <atomic>
-#include <barrier>
-#include <cstdint>
+// kernels.inc (everything inside its anonymous namespace) and builds this file with the host compiler; hip_on_host.hpp is the
+// device language on host threads.
+#include <cmath>
 #include <cstdio>
 #include <cstring>
-#include <functional>
 #include <random>
-#include <thread>
-#include <vector>
 #include "uwip.h"
 #include "jpeg.hpp"
 #include "jpeg_tables.hpp"
-struct d3 { unsigned x = 1, y = 1, z = 1; };
-static thread_local d3 threadIdx, blockIdx, blockDim;
-static std::barrier<> *g_bar;
-#define __global__ static
-#define __device__ static
-#define __forceinline__ inline
-#define __shared__ static
-#define __launch_bounds__(x)
-#define __restrict__
-static void __syncthreads() { g_bar->arrive_and_wait(); }
-static uint32_t atomicOr(uint32_t *p, uint32_t v) { return __atomic_fetch_or(p, v, __ATOMIC_SEQ_CST); }
-static uint32_t atomicAdd(uint32_t *p, uint32_t v) { return __atomic_fetch_add(p, v, __ATOMIC_SEQ_CST); }
-static int __clz(int v) { return v ? __builtin_clz((unsigned)v) : 32; }
-using std::min; using std::max;
-struct uint4 { uint32_t x, y, z, w; };
-static uint4 make_uint4(uint32_t a, uint32_t b, uint32_t c, uint32_t d) { return {a, b, c, d}; }
-static unsigned uwip_cdiv(size_t a, size_t b) { return (unsigned)((a + b - 1) / b); }
-// block-wide helpers of device_utils.hpp, restated with a shared array
-static uint32_t g_vals[256];
-static uint32_t block256_incl_scan_u32(uint32_t v, uint32_t *)
-{
-    __syncthreads(); g_vals[threadIdx.x] = v; __syncthreads();
-    uint32_t s = 0; for (unsigned i = 0; i <= threadIdx.x; ++i) s += g_vals[i];
-    __syncthreads(); return s;
-}
-static uint32_t block256_sum_u32(uint32_t v, uint32_t *)
-{
-    __syncthreads(); g_vals[threadIdx.x] = v; __syncthreads();
-    uint32_t s = 0; for (unsigned i = 0; i < 256; ++i) s += g_vals[i];
-    __syncthreads(); return s;
-}
+#include "hip_on_host.hpp"
 #include "kernels.inc"
-template <class F> static void launch(unsigned gx, unsigned gy, unsigned bs, F f)
-{
-    for (unsigned by = 0; by < gy; ++by) for (unsigned bx = 0; bx < gx; ++bx) {
-        std::barrier<> bar(bs); g_bar = &bar;
-        std::memset(g_vals, 0, sizeof g_vals);
-        std::vector<std::thread> th;
-        for (unsigned t = 0; t < bs; ++t) th.emplace_back([=, &bar] { g_bar = &bar; threadIdx.x = t; blockIdx.x = bx; blockIdx.y = by; blockDim.x = bs; f(); });
-        for (auto &t : th) t.join();
-    }
-}
 static int encode(const uint8_t *img, int F, int rows, int cols, int nc, size_t step, size_t fs, int quality, uint8_t *d_streams, size_t slot_bytes, int64_t *d_sizes)
 {
     quality = clamp_quality(quality);
@@ -88,14 +43,14 @@ static int encode(const uint8_t *img, int F, int rows, int cols, int nc, size_t 
     uint32_t *ffemit = chunkcnt + (size_t)F * nchunk, *notff = ffemit + F;
     std::memset(ffemit, 0, ((size_t)F + (size_t)F * (nwg_emit + 1)) * sizeof(uint32_t));
     const Offs o{blkoff, wgbase, totbits, nwg_bits};
-    launch(nwg_bits, F, 256, [=] { k_jpeg_transform(img, g, cst, coef); });
-    launch(nwg_bits, F, kBitsWG, [=] { k_jpeg_bits(coef, g, huff, blkoff, wgsum, nwg_bits); });
-    launch(F, 1, 256, [=] { k_jpeg_scan_bits(wgsum, wgbase, totbits, nwg_bits); });
-    launch(uwip_cdiv((size_t)nwg_emit, 256), F, 256, [=] { k_jpeg_zero_shared(g, o, cst, slot_bytes, ubuf, ustride, nwg_emit); });
-    launch(nwg_emit, F, kEmitWG, [=] { k_jpeg_emit(coef, g, huff, o, cst, slot_bytes, ubuf, ustride, ffemit, notff, nwg_emit); });
-    launch(nchunk, F, 256, [=] { k_jpeg_ffcount(ubuf, ustride, totbits, cst, slot_bytes, chunkcnt, nchunk); });
-    launch(F, 1, 256, [=] { k_jpeg_finish(chunkcnt, chunkbase, nchunk, g, o, cst, ffemit, notff, nwg_emit, needed); });
-    launch(nchunk, F, 256, [=] { k_jpeg_assemble(ubuf, ustride, totbits, chunkbase, nchunk, cst, needed, d_streams, slot_bytes, d_sizes); });
+    launch(nwg_bits, F, 256, true, [=] { k_jpeg_transform(img, g, cst, coef); });
+    launch(nwg_bits, F, kBitsWG, true, [=] { k_jpeg_bits(coef, g, huff, blkoff, wgsum, nwg_bits); });
+    launch(F, 1, 256, true, [=] { k_jpeg_scan_bits(wgsum, wgbase, totbits, nwg_bits); });
+    launch(uwip_cdiv((size_t)nwg_emit, 256), F, 256, true, [=] { k_jpeg_zero_shared(g, o, cst, slot_bytes, ubuf, ustride, nwg_emit); });
+    launch(nwg_emit, F, kEmitWG, true, [=] { k_jpeg_emit(coef, g, huff, o, cst, slot_bytes, ubuf, ustride, ffemit, notff, nwg_emit); });
+    launch(nchunk, F, 256, true, [=] { k_jpeg_ffcount(ubuf, ustride, totbits, cst, slot_bytes, chunkcnt, nchunk); });
+    launch(F, 1, 256, true, [=] { k_jpeg_finish(chunkcnt, chunkbase, nchunk, g, o, cst, ffemit, notff, nwg_emit, needed); });
+    launch(nchunk, F, 256, true, [=] { k_jpeg_assemble(ubuf, ustride, totbits, chunkbase, nchunk, cst, needed, d_streams, slot_bytes, d_sizes); });
     return 0;
 }
 int main()

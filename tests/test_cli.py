@@ -100,6 +100,29 @@ def test_jpeg_codec_against_pillow(tmp_path):
     assert im.mode == "L" and np.abs(np.asarray(im).astype(int) - g.astype(int)).mean() < 2.0
 
 
+def test_jpeg_header_is_the_one_pillow_writes(tmp_path):
+    """The header writer of csrc/jpeg_tables.hpp (shared by the host and the device encoder) against something outside the
+    project: the quantisation tables of an `imgconv` stream are the ones Pillow's libjpeg writes at quality 95, and SOI..SOS
+    is 623 bytes for a colour stream, 328 for a grey one."""
+    import io
+    _build()
+    conv = os.path.join(BIN, "imgconv")
+    colour = synth.uw_stream(0, 1, 17, 33)[0]
+    for name, img, hdr in (("colour", colour, 623), ("grey", np.ascontiguousarray(colour[:16, :16, 1]), 328)):
+        a, j = str(tmp_path / (name + ".png")), str(tmp_path / (name + ".jpg"))
+        pil = Image.fromarray(img if img.ndim == 2 else np.ascontiguousarray(img[..., ::-1]))
+        pil.save(a)
+        assert subprocess.run([conv, a, j] + (["grey"] if img.ndim == 2 else []), capture_output=True, timeout=120).returncode == 0
+        buf = io.BytesIO()
+        pil.save(buf, format="JPEG", quality=95, subsampling=2)
+        ours, theirs = Image.open(j), Image.open(io.BytesIO(buf.getvalue()))
+        assert ours.size == theirs.size and ours.mode == theirs.mode == ("L" if img.ndim == 2 else "RGB")
+        assert {k: list(v) for k, v in ours.quantization.items()} == {k: list(v) for k, v in theirs.quantization.items()}, name
+        s = open(j, "rb").read()
+        sos = s.index(b"\xff\xda")
+        assert sos + 2 + ((s[sos + 2] << 8) | s[sos + 3]) == hdr, name
+
+
 @pytest.mark.gpu
 def test_histretch_cli_config0_640x480_png(tmp_path, orc):
     """BASELINE config 0: histretch on one 640x480 PNG (here through the HIP path)."""
@@ -319,7 +342,8 @@ def _asan_tool(tmp_path, name, source):
     src, exe = str(tmp_path / (name + ".cpp")), str(tmp_path / name)
     open(src, "w").write(source)
     subprocess.run(["g++", "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
-                    "-I" + os.path.join(ROOT, "cli"), src, "-o", exe, "-lz"], check=True, timeout=300)
+                    "-I" + os.path.join(ROOT, "cli"), "-I" + os.path.join(ROOT, "uwimageproc_amd", "csrc"), src, "-o", exe, "-lz"],
+                   check=True, timeout=300)
     return exe
 
 

@@ -160,8 +160,9 @@ def test_host_only_streams_are_reported_not_decoded(emu):
 
 
 def test_mutated_headers_are_accepted_or_rejected_as_the_host_decoder_does(emu):
-    """jpeg_parse.hpp restates the header walk of jpeg::decode: with one header byte changed the two must still agree on
-    whether the stream decodes, and on the pixels where it does."""
+    """jpeg_parse.hpp is the header walk of both decoders: with one header byte changed they must still agree on whether
+    the stream decodes (PARSE_BAD is the host decoder's `false`; a host-only stream is one the host decodes), and on the
+    pixels where it does."""
     s = js.pil_stream(js.content(17, 33), 90, 2, restart_marker_blocks=3)
     a = js.segment_start(s)
     rng = np.random.default_rng(5)

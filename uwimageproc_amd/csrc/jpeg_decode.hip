@@ -1,8 +1,8 @@
 // Baseline JPEG decoding of a batch on the device: cv::imread / cv::imdecode without the host codec and without raw pixels on
-// the link.  The arithmetic restates jpeg::decode of cli/jpeg.hpp (the host codec of the CLIs) step for step, so a frame with
+// the link.  The arithmetic follows jpeg::decode of cli/jpeg.hpp (the host codec of the CLIs) step for step, so a frame with
 // status 0 holds the same bytes: Huffman decoding with the host's rule for bits past the end of a segment (zeros), the
-// clamped dequantisation, jidctint in 64-bit temporaries, jdsample's fancy h2v1 / h2v2 upsampling, jdcolor's fixed point.
-// The header is parsed on the host (jpeg_parse.hpp); only the entropy-coded segments and one descriptor per frame are
+// clamped dequantisation and jidctint in 64-bit temporaries (jpeg_core.hpp, shared with the host), jdsample's fancy h2v1 /
+// h2v2 upsampling, jdcolor's fixed point.  The header is parsed on the host (jpeg_parse.hpp, the host decoder's parse); only the entropy-coded segments and one descriptor per frame are
 // uploaded.  The stages, all on the context's stream, none waits for the host:
 //   k_jpd_unstuff   one workgroup per frame, 4 KiB per step (count, scan, copy with a running base): FF 00 -> FF, RSTn taken
 //                   out and its place recorded as the start of the next restart interval, stop at any other marker; then
@@ -28,6 +28,7 @@
 // without touching memory.
 #include "uwip_internal.hpp"
 #include "device_utils.hpp"
+#include "jpeg_core.hpp"
 #include "jpeg_parse.hpp"
 #include <cstring>
 
@@ -35,6 +36,10 @@ namespace {
 
 using uwip_jpeg::DecFrame;
 using uwip_jpeg::DecHuff;
+using uwip_jpeg::clamp_coef;
+using uwip_jpeg::descale64;
+using uwip_jpeg::extend;
+using uwip_jpeg::idct_pass;
 
 constexpr int kSubBytes = 128;                  // subsequence length (the device JPEG decoder)
 constexpr uint32_t kSubBits = kSubBytes * 8;
@@ -185,8 +190,6 @@ __device__ __forceinline__ bool huff(const DecHuff &h, uint32_t v, uint32_t &len
     return true;
 }
 
-__device__ __forceinline__ int extend(int v, int t) { return v < (1 << (t - 1)) ? v - (1 << t) + 1 : v; }
-
 // Decodes symbols from state `st` while the bit position is before `ebit` (WRITE: and, in the last subsequence of an interval,
 // on into the zeros behind it) and, WRITE, the block is before `limit`.  Returns the exit state, kInvalid after an undecodable
 // symbol; nblk: WRITE: the first block on entry, the block reached on exit; else the blocks completed.
@@ -194,9 +197,7 @@ template <bool WRITE>
 __device__ uint64_t decode_run(const Tabs &t, const DecFrame &d, const uint8_t *ubuf, uint32_t a0, uint32_t len, uint64_t st,
                                uint32_t ebit, bool last, uint32_t &nblk, uint32_t limit, int16_t *coef)
 {
-    constexpr uint8_t ZZ[64] = {0,  1,  8,  16, 9,  2,  3,  10, 17, 24, 32, 25, 18, 11, 4,  5,  12, 19, 26, 33, 40, 48,
-                                41, 34, 27, 20, 13, 6,  7,  14, 21, 28, 35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23,
-                                30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63};
+    constexpr uint8_t ZZ[64] = UWIP_JPEG_ZIGZAG_INIT;
     uint32_t p = (uint32_t)(st >> 32), b = ((uint32_t)st >> 8) & 0xFFu, k = (uint32_t)st & 0xFFu;
     const uint32_t bpm = (uint32_t)d.bpm, lenbits = len * 8u;
     // the blocks of an MCU at which components 1 and 2 start (one component: never), in registers for the symbol loop
@@ -448,31 +449,6 @@ __global__ __launch_bounds__(256) void k_jpd_dc(DecBufs B)
 }
 
 // ---- inverse DCT ------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ int64_t descale64(int64_t x, int n) { return (x + ((int64_t)1 << (n - 1))) >> n; }
-
-// one pass of jidctint in 64-bit temporaries, as jpeg::idct_islow: no signed overflow for |in| <= 2^20 (first pass) and for
-// what the first pass can return (second pass)
-__device__ __forceinline__ void idct_pass(const int64_t in[8], int64_t o[8])
-{
-    constexpr int64_t F0298 = 2446, F0390 = 3196, F0541 = 4433, F0765 = 6270, F0899 = 7373, F1175 = 9633, F1501 = 12299,
-                      F1847 = 15137, F1961 = 16069, F2053 = 16819, F2562 = 20995, F3072 = 25172;
-    int64_t z2 = in[2], z3 = in[6];
-    int64_t z1 = (z2 + z3) * F0541;
-    int64_t tmp2 = z1 + z3 * (-F1847), tmp3 = z1 + z2 * F0765;
-    int64_t tmp0 = (in[0] + in[4]) * (1 << 13), tmp1 = (in[0] - in[4]) * (1 << 13);
-    const int64_t tmp10 = tmp0 + tmp3, tmp13 = tmp0 - tmp3, tmp11 = tmp1 + tmp2, tmp12 = tmp1 - tmp2;
-    tmp0 = in[7]; tmp1 = in[5]; tmp2 = in[3]; tmp3 = in[1];
-    z1 = tmp0 + tmp3; z2 = tmp1 + tmp2; z3 = tmp0 + tmp2;
-    int64_t z4 = tmp1 + tmp3;
-    const int64_t z5 = (z3 + z4) * F1175;
-    tmp0 *= F0298; tmp1 *= F2053; tmp2 *= F3072; tmp3 *= F1501;
-    z1 *= -F0899; z2 *= -F2562; z3 *= -F1961; z4 *= -F0390;
-    z3 += z5; z4 += z5;
-    tmp0 += z1 + z3; tmp1 += z2 + z4; tmp2 += z2 + z3; tmp3 += z1 + z4;
-    o[0] = tmp10 + tmp3; o[7] = tmp10 - tmp3; o[1] = tmp11 + tmp2; o[6] = tmp11 - tmp2;
-    o[2] = tmp12 + tmp1; o[5] = tmp12 - tmp1; o[3] = tmp13 + tmp0; o[4] = tmp13 - tmp0;
-}
-
 __global__ __launch_bounds__(64) void k_jpd_idct(DecBufs B)
 {
     const int f = blockIdx.y;
@@ -490,10 +466,7 @@ __global__ __launch_bounds__(64) void k_jpd_idct(DecBufs B)
     const uint16_t *qt = d.qt[c];
     int64_t ws[64];
 #pragma unroll
-    for (int i = 0; i < 64; ++i) {
-        const int64_t v = (int64_t)src[i] * (int64_t)qt[i];
-        ws[i] = v > (1 << 20) ? (1 << 20) : (v < -(1 << 20) ? -(1 << 20) : v);       // jpeg::clamp_coef
-    }
+    for (int i = 0; i < 64; ++i) ws[i] = clamp_coef((int64_t)src[i] * (int64_t)qt[i]);
 #pragma unroll
     for (int col = 0; col < 8; ++col) {
         int64_t in[8], o[8];
@@ -632,6 +605,7 @@ UWIP_API int uwip_jpeg_decode(uwip_ctx *ctx, const uint8_t *const *h_streams, co
     // The page-locked staging buffer holds the descriptors, then the segments.  It is free again once the previous call's
     // upload has finished: poll that event (the stream is not drained) before the buffer is touched -- or grown, which frees it.
     static_assert(sizeof(DecFrame) % 16 == 0, "the segments follow the descriptors at a 16-byte boundary");
+    static_assert(sizeof(DecFrame) == 9056, "the kernels and the host decoder read one layout");
     if (!ctx->jpd_ev) UWIP_HIP(ctx, hipEventCreateWithFlags(&ctx->jpd_ev, hipEventDisableTiming));
     else UWIP_HIP(ctx, uwip_event_wait(ctx->jpd_ev, 200));
     const size_t hdr = (size_t)n * sizeof(DecFrame);

@@ -1,7 +1,8 @@
 // Baseline JPEG encoding of a batch on the device: cv::imwrite(".jpg") without the trip to the host.
-// The arithmetic restates jpeg::encode of cli/jpeg.hpp (the host codec the CLIs write their files with) step for step, so
-// the streams are the same bytes: rgb_ycc conversion, 2x2 chroma box with the alternating 1, 2 bias, jfdctint, the division
-// quantiser, the Annex K Huffman tables, byte stuffing.  Everything but the DC difference and the bit position of a block is
+// The arithmetic follows jpeg::encode of cli/jpeg.hpp (the host codec the CLIs write their files with) step for step, so
+// the streams are the same bytes: rgb_ycc conversion, 2x2 chroma box with the alternating 1, 2 bias, jfdctint (jpeg_core.hpp,
+// shared with the host), the division quantiser, the Annex K Huffman tables and the header (jpeg_tables.hpp, shared), byte
+// stuffing.  Everything but the DC difference and the bit position of a block is
 // independent per 8x8 block, so the frame goes through five streaming stages:
 //   k_jpeg_transform  one thread per block: samples (edge-replicated to the MCU-padded size) -> FDCT -> quantised
 //                     coefficients, zig-zag order, int16, in the workspace "jpeg.coef";
@@ -18,10 +19,13 @@
 // The unstuffed buffer keeps the stream as big-endian 32-bit words: byte k is bits 31-8(k&3) .. 24-8(k&3) of word k / 4.
 #include "uwip_internal.hpp"
 #include "device_utils.hpp"
+#include "jpeg_core.hpp"
 #include "jpeg_tables.hpp"
 #include <cstring>
 
 namespace {
+
+using uwip_jpeg::fdct_pass;
 
 constexpr int kBitsWG = 256;        // blocks per workgroup of k_jpeg_bits (one thread each)
 constexpr int kEmitWG = 128;        // blocks per workgroup of k_jpeg_emit
@@ -49,32 +53,6 @@ struct Geo {
     int mcux, nblk;                 // MCUs per row; blocks per frame in scan order
     size_t step, fs;
 };
-
-__device__ __forceinline__ int32_t descale(int32_t x, int n) { return (x + (1 << (n - 1))) >> n; }
-
-// jfdctint (CONST_BITS 13, PASS1_BITS 2): 64 samples - 128 -> coefficients scaled by 8
-__device__ __forceinline__ void fdct_pass(int32_t &p0, int32_t &p1, int32_t &p2, int32_t &p3, int32_t &p4, int32_t &p5, int32_t &p6,
-                                          int32_t &p7, const bool rows)
-{
-    constexpr int32_t F0298 = 2446, F0390 = 3196, F0541 = 4433, F0765 = 6270, F0899 = 7373, F1175 = 9633, F1501 = 12299,
-                      F1847 = 15137, F1961 = 16069, F2053 = 16819, F2562 = 20995, F3072 = 25172;
-    int32_t tmp0 = p0 + p7, tmp7 = p0 - p7, tmp1 = p1 + p6, tmp6 = p1 - p6;
-    int32_t tmp2 = p2 + p5, tmp5 = p2 - p5, tmp3 = p3 + p4, tmp4 = p3 - p4;
-    const int32_t tmp10 = tmp0 + tmp3, tmp13 = tmp0 - tmp3, tmp11 = tmp1 + tmp2, tmp12 = tmp1 - tmp2;
-    const int sh = rows ? 13 - 2 : 13 + 2;
-    if (rows) { p0 = (tmp10 + tmp11) * 4; p4 = (tmp10 - tmp11) * 4; }
-    else      { p0 = descale(tmp10 + tmp11, 2); p4 = descale(tmp10 - tmp11, 2); }
-    int32_t z1 = (tmp12 + tmp13) * F0541;
-    p2 = descale(z1 + tmp13 * F0765, sh); p6 = descale(z1 + tmp12 * (-F1847), sh);
-    z1 = tmp4 + tmp7;
-    int32_t z2 = tmp5 + tmp6, z3 = tmp4 + tmp6, z4 = tmp5 + tmp7;
-    const int32_t z5 = (z3 + z4) * F1175;
-    tmp4 *= F0298; tmp5 *= F2053; tmp6 *= F3072; tmp7 *= F1501;
-    z1 *= -F0899; z2 *= -F2562; z3 *= -F1961; z4 *= -F0390;
-    z3 += z5; z4 += z5;
-    p7 = descale(tmp4 + z1 + z3, sh); p5 = descale(tmp5 + z2 + z4, sh);
-    p3 = descale(tmp6 + z2 + z3, sh); p1 = descale(tmp7 + z1 + z4, sh);
-}
 
 // where block b of the scan lies: component (0 = Y, 1 = Cb, 2 = Cr) and the top-left luma pixel of what it covers
 __device__ __forceinline__ void block_place(const Geo &g, int b, int &comp, int &x0, int &y0)
@@ -154,9 +132,7 @@ __global__ __launch_bounds__(256) void k_jpeg_transform(const uint8_t *__restric
     for (int c = 0; c < 8; ++c)
         fdct_pass(d[c], d[8 + c], d[16 + c], d[24 + c], d[32 + c], d[40 + c], d[48 + c], d[56 + c], false);
     const int32_t *qv = s_qv[comp ? 1 : 0];
-    constexpr uint8_t ZZ[64] = {0,  1,  8,  16, 9,  2,  3,  10, 17, 24, 32, 25, 18, 11, 4,  5,  12, 19, 26, 33, 40, 48,
-                                41, 34, 27, 20, 13, 6,  7,  14, 21, 28, 35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23,
-                                30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63};
+    constexpr uint8_t ZZ[64] = UWIP_JPEG_ZIGZAG_INIT;
     uint32_t pk[32];
 #pragma unroll
     for (int i = 0; i < 64; ++i) {
@@ -434,47 +410,16 @@ __global__ __launch_bounds__(256) void k_jpeg_assemble(const uint32_t *__restric
 
 int clamp_quality(int q) { return q < 1 ? 1 : (q > 100 ? 100 : q); }
 
-// SOI, APP0, DQT, SOF0, DHT, SOS and the quantisers for (rows, cols, nc, quality)
+// the quantisers and SOI .. SOS for (rows, cols, nc, quality)
 void build_const(int rows, int cols, int nc, int quality, JpegConst &c)
 {
-    using namespace uwip_jpeg;
-    const int scale = quality < 50 ? 5000 / quality : 200 - 2 * quality;
     uint8_t q[2][64];
-    for (int i = 0; i < 64; ++i) {
-        const int a = (STD_LUM_Q[i] * scale + 50) / 100, b = (STD_CHR_Q[i] * scale + 50) / 100;
-        q[0][i] = (uint8_t)(a < 1 ? 1 : (a > 255 ? 255 : a));
-        q[1][i] = (uint8_t)(b < 1 ? 1 : (b > 255 ? 255 : b));
-    }
+    uwip_jpeg::scaled_quant(quality, q);
     for (int t = 0; t < 2; ++t)
-        for (int i = 0; i < 64; ++i) c.qv[t][i] = (int32_t)q[t][ZIGZAG[i]] << 3;
-    uint8_t *h = c.hdr;
-    size_t n = 0;
-    auto put = [&](int v) { h[n++] = (uint8_t)v; };
-    auto w16 = [&](int v) { put(v >> 8); put(v); };
-    put(0xFF); put(0xD8);
-    static const uint8_t jfif[18] = {0xFF, 0xE0, 0, 16, 'J', 'F', 'I', 'F', 0, 1, 1, 0, 0, 1, 0, 1, 0, 0};
-    for (uint8_t v : jfif) put(v);
-    for (int t = 0; t < (nc == 3 ? 2 : 1); ++t) {
-        put(0xFF); put(0xDB); w16(67); put(t);
-        for (int i = 0; i < 64; ++i) put(q[t][ZIGZAG[i]]);
-    }
-    const int hs = nc == 3 ? 2 : 1;
-    put(0xFF); put(0xC0); w16(8 + 3 * nc); put(8); w16(rows); w16(cols); put(nc);
-    for (int i = 0; i < nc; ++i) { put(i + 1); put(i == 0 ? (hs << 4 | hs) : 0x11); put(i ? 1 : 0); }
-    auto dht = [&](int cls_id, const uint8_t *bits, const uint8_t *vals, int cnt) {
-        put(0xFF); put(0xC4); w16(19 + cnt); put(cls_id);
-        for (int i = 1; i < 17; ++i) put(bits[i]);
-        for (int i = 0; i < cnt; ++i) put(vals[i]);
-    };
-    dht(0x00, DC_LUM_BITS, DC_VALS, 12); dht(0x10, AC_LUM_BITS, AC_LUM_VALS, 162);
-    if (nc == 3) { dht(0x01, DC_CHR_BITS, DC_VALS, 12); dht(0x11, AC_CHR_BITS, AC_CHR_VALS, 162); }
-    put(0xFF); put(0xDA); w16(6 + 2 * nc); put(nc);
-    for (int i = 0; i < nc; ++i) { put(i + 1); put(i ? 0x11 : 0x00); }
-    put(0); put(63); put(0);
-    c.hdr_len = (uint32_t)n;
+        for (int i = 0; i < 64; ++i) c.qv[t][i] = (int32_t)q[t][uwip_jpeg::ZIGZAG[i]] << 3;
+    static_assert(kHdrMax >= uwip_jpeg::header_bytes(3), "JpegConst::hdr holds the longer header");
+    c.hdr_len = (uint32_t)uwip_jpeg::write_header(rows, cols, nc, q, c.hdr);
 }
-
-size_t header_bytes(int nc) { return nc == 3 ? 623 : 328; }
 
 int blocks_of(int rows, int cols, int nc, int *mcux_out)
 {
@@ -490,7 +435,7 @@ UWIP_API size_t uwip_jpeg_bound(int rows, int cols, int channels)
 {
     if (rows < 1 || cols < 1 || rows > 65535 || cols > 65535 || (channels != 1 && channels != 3)) return 0;
     const size_t nblk = (size_t)blocks_of(rows, cols, channels, nullptr);
-    return header_bytes(channels) + 2 * ((nblk * kMaxBlockBits + 7) / 8) + 2;
+    return uwip_jpeg::header_bytes(channels) + 2 * ((nblk * kMaxBlockBits + 7) / 8) + 2;
 }
 
 UWIP_API int uwip_jpeg_encode(uwip_ctx *ctx, const uwip_batch_u8 *frames, int quality, uint8_t *d_streams, size_t slot_bytes,

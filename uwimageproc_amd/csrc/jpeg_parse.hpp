@@ -1,6 +1,7 @@
-// The host half of the device JPEG decoder (jpeg_decode.hip): the header parse of jpeg::decode (cli/jpeg.hpp) restated with
-// the same rejections, and the per-frame descriptor the kernels read.  Host-only, no device needed: uwip_jpeg_info is this
-// parse alone, and tests/jpeg_decode_emulated.cpp feeds the kernels, run on host threads, from it.
+// The header parse of baseline JPEG, the one copy: SOI .. SOS into the per-frame descriptor that the kernels of the device
+// decoder (jpeg_decode.hip) read and that the host decoder of the CLIs (jpeg::decode, cli/jpeg.hpp) decodes from.  Host-only,
+// no device needed: uwip_jpeg_info is this parse alone, and tests/jpeg_decode_emulated.cpp feeds the kernels, run on host
+// threads, from it.
 #pragma once
 #include <cstdint>
 #include <cstring>
@@ -8,8 +9,8 @@
 
 namespace uwip_jpeg {
 
-// one Huffman table as the decoder reads it (jpeg::HuffTable's decoding half): 9-bit look-ahead, (length << 8) | symbol,
-// 0 = a longer code; maxcode[l] / valptr[l] for l = 10..16 (index 0 unused)
+// one Huffman table as the decoders read it: 9-bit look-ahead, (length << 8) | symbol, 0 = a longer code; maxcode[l] /
+// valptr[l] for l = 10..16 (index 0 unused)
 struct DecHuff {
     uint16_t lookup[512];
     int32_t maxcode[17];
@@ -37,12 +38,13 @@ struct DecFrame {
     DecHuff dc[3], ac[3];           // tables per component
 };
 
-// jpeg::HuffTable::build: false when the counts do not describe a prefix code
+// a table as DHT gives it, and the decoding tables built from it (T.81 Annex C, F.2.2.3)
 struct HuffSpec {
     uint8_t bits[17] = {0}, vals[256] = {0};
     bool present = false;
     int32_t maxcode[18], valptr[17];
     uint16_t lookup[512];
+    // false: the counts do not describe a prefix code (over-subscribed lengths, libjpeg's JERR_BAD_HUFF_TABLE)
     bool build()
     {
         present = false;
@@ -55,7 +57,7 @@ struct HuffSpec {
         p = 0;
         while (huffsize[p]) {
             while (huffsize[p] == si) huffcode[p++] = (uint16_t)code++;
-            if (code >= (1 << si)) return false;
+            if (code >= (1 << si)) return false;     // more codes of length si than the prefix tree has room for
             code <<= 1; si++;
         }
         p = 0;
@@ -93,14 +95,17 @@ inline void std_spec(HuffSpec &t, const uint8_t *bits, const uint8_t *vals, int 
 
 enum { PARSE_OK = 0, PARSE_BAD = -1, PARSE_HOST_ONLY = -3 };       // the values of UWIP_JPEG_BAD_STREAM / _HOST_ONLY
 
-// The walk of jpeg::decode from SOI to the end of SOS.  PARSE_BAD where jpeg::decode returns false before it reads the first
-// entropy-coded bit, or finds no scan at all.  On PARSE_OK / PARSE_HOST_ONLY the geometry, the quantisers and the tables of
-// `d` are filled in and the entropy-coded segment is buf[*seg .. len).  `d` may be null (uwip_jpeg_info: sizes only).
+// The walk from SOI to the end of SOS.  PARSE_BAD: not the baseline both decoders read (SOF0 / SOF1, 8 bit, 1 or 3 components
+// with sampling factors 1 or 2, one interleaved scan), a malformed segment, a table the scan names but no DHT or default
+// gives, or no scan at all.  On PARSE_OK / PARSE_HOST_ONLY (1x2 sampling: the host decoder alone upsamples it) the geometry,
+// the quantisers and the tables of `d` are filled in and the entropy-coded segment is buf[*seg .. len).  `d` may be null
+// (uwip_jpeg_info: sizes only).
 inline int parse(const uint8_t *buf, size_t len, int *rows, int *cols, int *channels, DecFrame *d, size_t *seg)
 {
     if (!buf || len < 4 || buf[0] != 0xFF || buf[1] != 0xD8) return PARSE_BAD;
     uint16_t qt[4][64] = {{0}};
     HuffSpec dc[4], ac[4];
+    // Motion-JPEG frames may omit DHT: the standard tables apply (overridden by any DHT)
     std_spec(dc[0], DC_LUM_BITS, DC_VALS, 12); std_spec(ac[0], AC_LUM_BITS, AC_LUM_VALS, 162);
     std_spec(dc[1], DC_CHR_BITS, DC_VALS, 12); std_spec(ac[1], AC_CHR_BITS, AC_CHR_VALS, 162);
     struct Comp { int id, h, v, tq, td, ta; } comp[3] = {};
@@ -143,7 +148,7 @@ inline int parse(const uint8_t *buf, size_t len, int *rows, int *cols, int *chan
             H = (s[1] << 8) | s[2]; W = (s[3] << 8) | s[4];
             const int n = s[5];
             if ((n != 1 && n != 3) || W <= 0 || H <= 0 || L < (size_t)(8 + 3 * n)) return PARSE_BAD;
-            if (have_sof) return PARSE_BAD;
+            if (have_sof) return PARSE_BAD;             // one frame per file
             ncomp = n;
             for (int i = 0; i < n; ++i) {
                 comp[i].id = s[6 + 3 * i]; comp[i].h = s[7 + 3 * i] >> 4; comp[i].v = s[7 + 3 * i] & 15; comp[i].tq = s[8 + 3 * i] & 3;
@@ -153,14 +158,14 @@ inline int parse(const uint8_t *buf, size_t len, int *rows, int *cols, int *chan
             }
             have_sof = true;
         } else if (m == 0xC2 || (m >= 0xC5 && m <= 0xCF && m != 0xC8 && m != 0xCC)) {
-            return PARSE_BAD;
+            return PARSE_BAD;                   // progressive / lossless / arithmetic
         } else if (m == 0xDD) {
             if (L < 4) return PARSE_BAD;
             restart = (s[0] << 8) | s[1];
         } else if (m == 0xDA) {
             if (!have_sof || L < 3) return PARSE_BAD;
             const int ns = s[0];
-            if (ns != ncomp || L < (size_t)(6 + 2 * ns)) return PARSE_BAD;
+            if (ns != ncomp || L < (size_t)(6 + 2 * ns)) return PARSE_BAD;      // one interleaved scan (what baseline encoders write)
             for (int i = 0; i < ns; ++i)
                 for (int c = 0; c < ncomp; ++c)
                     if (comp[c].id == s[1 + 2 * i]) { comp[c].td = s[2 + 2 * i] >> 4; comp[c].ta = s[2 + 2 * i] & 15; }

@@ -1,14 +1,21 @@
-// The Annex K tables of baseline JPEG (ITU-T T.81): the zig-zag order, the two quantisation tables and the four standard
-// Huffman tables, as the device encoder (jpeg_encode.hip) and the header it writes use them.  The library's own copy: the
-// host codec of the CLIs (cli/jpeg.hpp) keeps its own, and cli/jpegenc_check.cpp asserts at start that the two agree.
+// The Annex K tables of baseline JPEG (ITU-T T.81) -- the zig-zag order, the two quantisation tables, the four standard
+// Huffman tables -- and what every encoder here derives from them: the quantisers of a quality, the codes of a table, the
+// header of a stream.  The one copy: the host codec of the CLIs (cli/jpeg.hpp) and the device codec (jpeg_encode.hip,
+// jpeg_parse.hpp) both read these.
 #pragma once
+#include <cassert>
+#include <cstddef>
 #include <cstdint>
+
+// the zig-zag order as an initialiser: device code cannot index a namespace-scope host array at run time, so a kernel keeps
+// a function-local constexpr array initialised from this
+#define UWIP_JPEG_ZIGZAG_INIT                                                                                                  \
+    {0,  1,  8,  16, 9,  2,  3,  10, 17, 24, 32, 25, 18, 11, 4,  5,  12, 19, 26, 33, 40, 48, 41, 34, 27, 20, 13, 6,  7,  14, 21, 28, \
+     35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23, 30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63}
 
 namespace uwip_jpeg {
 
-static const uint8_t ZIGZAG[64] = {0,  1,  8,  16, 9,  2,  3,  10, 17, 24, 32, 25, 18, 11, 4,  5,  12, 19, 26, 33, 40, 48,
-                                   41, 34, 27, 20, 13, 6,  7,  14, 21, 28, 35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23,
-                                   30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63};
+static const uint8_t ZIGZAG[64] = UWIP_JPEG_ZIGZAG_INIT;
 
 static const uint8_t STD_LUM_Q[64] = {16, 11, 10, 16, 24,  40,  51,  61,  12, 12, 14, 19, 26,  58,  60,  55,  14, 13, 16, 24, 40,  57,
                                       69, 56, 14, 17, 22,  29,  51,  87,  80, 62, 18, 22, 37,  56,  68,  109, 103, 77, 24, 35, 55, 64,
@@ -51,6 +58,51 @@ inline void build_codes(const uint8_t *bits, const uint8_t *vals, uint32_t *out2
         for (int i = 0; i < bits[l]; ++i, ++p) out256[vals[p]] = code++ | ((uint32_t)l << 16);
         code <<= 1;
     }
+}
+
+// the two quantisation tables (luma, chroma; natural order) at a quality of 1..100 (clamped), libjpeg's jpeg_set_quality
+inline void scaled_quant(int quality, uint8_t q[2][64])
+{
+    quality = quality < 1 ? 1 : (quality > 100 ? 100 : quality);
+    const int scale = quality < 50 ? 5000 / quality : 200 - 2 * quality;
+    for (int i = 0; i < 64; ++i) {
+        const int a = (STD_LUM_Q[i] * scale + 50) / 100, b = (STD_CHR_Q[i] * scale + 50) / 100;
+        q[0][i] = (uint8_t)(a < 1 ? 1 : (a > 255 ? 255 : a));
+        q[1][i] = (uint8_t)(b < 1 ? 1 : (b > 255 ? 255 : b));
+    }
+}
+
+// SOI .. SOS of a stream of nc components (1: grey; 3: YCbCr 4:2:0), stated on its own
+constexpr size_t header_bytes(int nc) { return nc == 3 ? 623 : 328; }
+
+// Writes SOI, APP0 (JFIF), DQT, SOF0, DHT (the standard tables) and SOS into h, which holds header_bytes(nc); returns the length.
+inline size_t write_header(int rows, int cols, int nc, const uint8_t q[2][64], uint8_t *h)
+{
+    size_t n = 0;
+    auto put = [&](int v) { h[n++] = (uint8_t)v; };
+    auto w16 = [&](int v) { put(v >> 8); put(v); };
+    put(0xFF); put(0xD8);
+    static const uint8_t jfif[18] = {0xFF, 0xE0, 0, 16, 'J', 'F', 'I', 'F', 0, 1, 1, 0, 0, 1, 0, 1, 0, 0};
+    for (uint8_t v : jfif) put(v);
+    for (int t = 0; t < (nc == 3 ? 2 : 1); ++t) {
+        put(0xFF); put(0xDB); w16(67); put(t);
+        for (int i = 0; i < 64; ++i) put(q[t][ZIGZAG[i]]);
+    }
+    const int hs = nc == 3 ? 2 : 1;
+    put(0xFF); put(0xC0); w16(8 + 3 * nc); put(8); w16(rows); w16(cols); put(nc);
+    for (int i = 0; i < nc; ++i) { put(i + 1); put(i == 0 ? (hs << 4 | hs) : 0x11); put(i ? 1 : 0); }
+    auto dht = [&](int cls_id, const uint8_t *bits, const uint8_t *vals, int cnt) {
+        put(0xFF); put(0xC4); w16(19 + cnt); put(cls_id);
+        for (int i = 1; i < 17; ++i) put(bits[i]);
+        for (int i = 0; i < cnt; ++i) put(vals[i]);
+    };
+    dht(0x00, DC_LUM_BITS, DC_VALS, 12); dht(0x10, AC_LUM_BITS, AC_LUM_VALS, 162);
+    if (nc == 3) { dht(0x01, DC_CHR_BITS, DC_VALS, 12); dht(0x11, AC_CHR_BITS, AC_CHR_VALS, 162); }
+    put(0xFF); put(0xDA); w16(6 + 2 * nc); put(nc);
+    for (int i = 0; i < nc; ++i) { put(i + 1); put(i ? 0x11 : 0x00); }
+    put(0); put(63); put(0);
+    assert(n == header_bytes(nc));
+    return n;
 }
 
 }  // namespace uwip_jpeg
