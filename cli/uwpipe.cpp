@@ -4,7 +4,7 @@
 //   calcOverlap of every frame against its predecessor (modules/videostrip/src/videostrip.cpp:192-289)
 // on the frames of a Motion-JPEG .avi or of a frame list, in batches through page-locked host buffers
 // (uwip_pipe_step_host: batch k + 1 is uploaded and batch k - 1 leaves while batch k's kernels run).
-//   uwpipe [-b N] [-c LETTERS] [-w N] [--guard-s] [--min6] [--relative-threshold] [--png] [--device-jpeg] [--device-decode]
+//   uwpipe [-b N] [-c LETTERS] [-w N] [--guard-s] [--min6] [--relative-threshold] [--png] [--device-jpeg] [--device-png] [--device-decode]
 //          [--keyframes [-k N] [-p X] [--lookback D]] <video.avi | frame_list.txt> <output_prefix>
 // writes <prefix>NNNN.jpg (the enhanced frames) and <prefix>uwpipe_report.txt (TSV: ID, Filename, Overlap, BS, CL).
 // --keyframes: the overlap stage runs videostrip's key-frame selector (main.cpp:284-394) on the enhanced frames, on the
@@ -13,6 +13,7 @@
 // overlap against the current key frame (nan: not compared).
 // --device-jpeg: the enhanced frames of a step are encoded on the device (uwip_jpeg_encode_host on the pipe's context, from
 // the step's frames in the staging area) and the files are written from the returned streams: the same bytes as without it.
+// --device-png: the files are .png, encoded on the device in the same way (uwip_png_encode_host): the pixels of --png, other bytes.
 // --device-decode (.avi, or a list of .jpg files): the compressed frames of a step are decoded on the pipe's context into a
 // device batch (uwip_jpeg_decode_host), uwip_pipe_step runs on the resident frames, and the results leave as streams
 // (--device-jpeg) or by a plain download; a frame with a negative status is decoded on the host and copied into its slot.
@@ -31,12 +32,13 @@ int main(int argc, char **argv)
     if (a.pos.size() < 2 || a.has("h") || a.has("help")) {
         std::printf("uwpipe - bgdehaze -> histretch -> aclahe -> overlap of every frame against its predecessor\n"
                     "usage: uwpipe [-b N] [-c LETTERS] [-w N] [--guard-s] [--min6] [--relative-threshold] [--png] [--device-jpeg]\n"
-                    "              [--device-decode] [--keyframes [-k N] [-p X] [--lookback D]] <video.avi (Motion-JPEG) | frame_list.txt> <output_prefix>\n"
+                    "              [--device-png] [--device-decode] [--keyframes [-k N] [-p X] [--lookback D]] <video.avi (Motion-JPEG) | frame_list.txt> <output_prefix>\n"
                     "  -b N      frames per step (default 8)\n"
                     "  -c L      histretch letters (default RGB)\n"
                     "  -w N      bgdehaze window (default 15)\n"
                     "  --guard-s / --min6 / --relative-threshold   the library's opt-in deviations from the reference's rules (uwip.h)\n"
                     "  --device-jpeg   encode the .jpg files on the device (same bytes; ignored with --png)\n"
+                    "  --device-png    write .png files encoded on the device (the pixels of --png; the bytes differ)\n"
                     "  --device-decode decode the input JPEG frames on the device (same files; a frame the device decoder leaves is decoded on the host)\n"
                     "  --keyframes   select key frames as videostrip does (report: <prefix>videostrip_report.txt)\n"
                     "  -k N          frames of the refinement window (default 11)\n"
@@ -45,7 +47,7 @@ int main(int argc, char **argv)
         return 0;
     }
     const std::string InputFile = a.pos[0], OutputFile = a.pos[1];
-    const char *ext = a.has("png") ? "png" : "jpg";
+    const char *ext = a.has("png") || a.has("device-png") ? "png" : "jpg";
     std::vector<std::string> frames;
     avi::Reader video;
     const bool is_avi = imgio::ends_with(InputFile, ".avi");
@@ -122,7 +124,9 @@ int main(int argc, char **argv)
         };
         const size_t nb = (n + B - 1) / B;
         std::vector<int32_t> bs(B), cl(B);
-        const bool device_jpeg = a.has("device-jpeg") && !a.has("png");
+        // device_jpeg: the files come from device streams, JPEG or (device_png) PNG
+        const bool device_png = a.has("device-png");
+        const bool device_jpeg = device_png || (a.has("device-jpeg") && !a.has("png"));
         std::vector<uint8_t> jstreams(device_jpeg ? fbytes * B : 0);      // slot = the raw frame size
         std::vector<int64_t> jsizes(B, -1);
         uint64_t prev_up = 0;                    // upload ticket of the step that last read h_in[(k + 1) & 1]
@@ -197,7 +201,8 @@ int main(int argc, char **argv)
                 uwip_batch_u8 bt{};
                 bt.data = (void *)d_frames; bt.rows = rows; bt.cols = cols; bt.channels = 3; bt.frames = B;
                 bt.step = (size_t)cols * 3; bt.frame_stride = fbytes;
-                CK(uwip_jpeg_encode_host(ctx, &bt, 95, jstreams.data(), fbytes, jsizes.data()), "uwip_jpeg_encode_host");
+                if (device_png) CK(uwip_png_encode_host(ctx, &bt, -1, jstreams.data(), fbytes, jsizes.data()), "uwip_png_encode_host");
+                else CK(uwip_jpeg_encode_host(ctx, &bt, 95, jstreams.data(), fbytes, jsizes.data()), "uwip_jpeg_encode_host");
             }
             for (int j = 0; j < B && k * B + j < n; ++j) {
                 const size_t i = k * B + j;

@@ -604,6 +604,36 @@ int uwip_jpeg_encode(uwip_ctx *ctx, const uwip_batch_u8 *frames, int quality, ui
 int uwip_jpeg_encode_host(uwip_ctx *ctx, const uwip_batch_u8 *frames, int quality, uint8_t *h_streams, size_t slot_bytes,
                           int64_t *h_sizes);
 
+/* ---- writing the frames: PNG on the device -------------------------------------------------------------------------------
+ * cv::imwrite(".png") for a batch, on the device: lossless; the bytes differ from OpenCV's and from cli/imgio.hpp's, the pixels
+ * do not.  8-bit frames with 1 channel (colour type 0) or 3 channels (BGR in, RGB in the file, colour type 2); any step /
+ * frame_stride / alignment, rows and cols 1..65535.  No interlace, no ancillary chunks: signature, IHDR, IDATs, IEND.
+ * filter: -1 is the adaptive choice, made per row: choose the type 0..4 whose filtered row has the smallest sum of
+ *   min(v, 256 - v) over its bytes; ties go to the lowest type number; row 0 uses the same rule with the row above taken as
+ *   zeros.  0..4 forces that type on every row.
+ * The zlib stream: the filtered bytes (rows x (1 + cols * channels)) are cut into chunks of uwip_png_chunk_bytes() = 32768
+ *   bytes and each chunk is coded on its own.  Tokens are zlib's Z_RLE parse: the first byte of a run is a literal, the equal
+ *   bytes that follow are matches at distance 1 of length 3..258, leftovers shorter than 3 are literals.  Each chunk is one
+ *   deflate block: stored (BTYPE 00) where that is not longer in bytes, else fixed (01) where that is not longer in bits, else
+ *   dynamic (10) with a literal/length code limited to 15 bits and a code-length code limited to 7.  Every chunk but the last
+ *   ends with an empty stored block (00 00 FF FF), the last block carries BFINAL; one IDAT per chunk, then one IDAT with the
+ *   Adler-32 of the filtered bytes.
+ * uwip_png_bound: the worst-case stream length of one frame, 0 for a bad geometry (host, pure, no device needed).  Derivation:
+ *   a chunk is never longer than its stored form, 5 bytes of block header and its bytes, plus the 5 bytes of the empty stored
+ *   block (3 bits, padding, LEN, NLEN) and the 12 of its IDAT's length, type and CRC: filtered bytes + 22 per chunk; per frame
+ *   signature and IHDR (33), the zlib header (2), the Adler-32's IDAT (16) and IEND (12): 63.
+ * uwip_png_encode: asynchronous on the context's stream.  Frame f's stream starts at d_streams + f * slot_bytes and d_sizes[f]
+ *   is its length; a frame whose stream is longer than slot_bytes writes nothing and reports -(needed length) -- a status, not
+ *   an error: the other frames of the batch are unaffected.  Without a device it fails with UWIP_ERR_HIP.
+ * uwip_png_encode_host: the same into host memory (frame f at h_streams + f * slot_bytes): encodes, waits, and copies only
+ *   the bytes each stream uses. */
+size_t uwip_png_bound(int rows, int cols, int channels);
+int uwip_png_chunk_bytes(void);
+int uwip_png_encode(uwip_ctx *ctx, const uwip_batch_u8 *frames, int filter, uint8_t *d_streams, size_t slot_bytes,
+                    int64_t *d_sizes);
+int uwip_png_encode_host(uwip_ctx *ctx, const uwip_batch_u8 *frames, int filter, uint8_t *h_streams, size_t slot_bytes,
+                         int64_t *h_sizes);
+
 /* ---- reading the frames: baseline JPEG on the device ---------------------------------------------------------------
  * cv::imread / cv::imdecode for a batch, on the device (jpeg::decode of cli/jpeg.hpp is the host form; where the status is 0,
  * the same pixels byte for byte, the host decoder's rules for a truncated segment included: bits past the end, or past a

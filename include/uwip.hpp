@@ -262,6 +262,34 @@ inline std::vector<std::vector<uint8_t>> imencode_jpeg(Context &c, const DeviceM
     return imencode_jpeg(c, *m.batch(), quality);
 }
 
+// ---- cv::imwrite(".png") / cv::imencode(".png") on the device ------------------------------------------------------
+// One PNG stream per frame of a device batch (uwip_png_encode_host): lossless, filter -1 = the adaptive choice per row.  The
+// slot is the frame's raw size and grows to uwip_png_bound for the rare batch with a frame that outgrows it (noise).
+inline std::vector<std::vector<uint8_t>> imencode_png(Context &c, const uwip_batch_u8 &frames, int filter = -1)
+{
+    const size_t F = (size_t)(frames.frames > 0 ? frames.frames : 0);
+    std::vector<std::vector<uint8_t>> out(F);
+    if (F == 0) return out;
+    size_t slot = (size_t)frames.rows * frames.cols * frames.channels + 1024;
+    std::vector<uint8_t> buf;
+    std::vector<int64_t> sizes(F);
+    for (int attempt = 0; attempt < 2; ++attempt) {
+        buf.resize(F * slot);
+        c.check(uwip_png_encode_host(c.get(), &frames, filter, buf.data(), slot, sizes.data()));
+        bool fits = true;
+        for (int64_t s : sizes) fits = fits && s >= 0;
+        if (fits) break;
+        if (attempt) throw Error(UWIP_ERR_INVALID, "uwip_png_encode_host: a stream exceeds uwip_png_bound");
+        slot = uwip_png_bound(frames.rows, frames.cols, frames.channels);
+    }
+    for (size_t f = 0; f < F; ++f) out[f].assign(buf.begin() + f * slot, buf.begin() + f * slot + (size_t)sizes[f]);
+    return out;
+}
+inline std::vector<std::vector<uint8_t>> imencode_png(Context &c, const DeviceMat &m, int filter = -1)
+{
+    return imencode_png(c, *m.batch(), filter);
+}
+
 // ---- cv::imdecode of JPEG streams on the device -------------------------------------------------------------------------
 // One frame of the device batch `out` per baseline JPEG / Motion-JPEG stream (uwip_jpeg_decode_host): where the returned
 // status is 0, the pixels of the CLIs' host decoder byte for byte; a negative status (UWIP_JPEG_BAD_STREAM / _SIZE_MISMATCH /

@@ -8,5 +8,6 @@ no CPU fallback.
 """
 from ._native import BatchU8, Context, Copier, PipeConfig, UwipError, batch_of, device_count, lib  # noqa: F401
 from . import jpeg  # noqa: F401
+from . import png  # noqa: F401
 
-__all__ = ["BatchU8", "Context", "Copier", "PipeConfig", "UwipError", "batch_of", "device_count", "jpeg", "lib"]
+__all__ = ["BatchU8", "Context", "Copier", "PipeConfig", "UwipError", "batch_of", "device_count", "jpeg", "lib", "png"]

@@ -184,6 +184,10 @@ SIGNATURES = {
     "uwip_jpeg_bound": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
     "uwip_jpeg_encode": (C.c_int, [_P, _B, C.c_int, _P, C.c_size_t, _P]),
     "uwip_jpeg_encode_host": (C.c_int, [_P, _B, C.c_int, _P, C.c_size_t, _P]),
+    "uwip_png_bound": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+    "uwip_png_chunk_bytes": (C.c_int, []),
+    "uwip_png_encode": (C.c_int, [_P, _B, C.c_int, _P, C.c_size_t, _P]),
+    "uwip_png_encode_host": (C.c_int, [_P, _B, C.c_int, _P, C.c_size_t, _P]),
     "uwip_jpeg_info": (C.c_int, [_P, C.c_size_t, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "uwip_jpeg_decode": (C.c_int, [_P, _P, _P, C.c_int, _B, _P, _P]),
     "uwip_jpeg_decode_host": (C.c_int, [_P, _P, _P, C.c_int, _B, _P, _P]),
