@@ -127,7 +127,8 @@ def test_colour_space_letters_as_written(ctx, orc, letters, shape):
 @pytest.mark.parametrize("space", [1, 2, 3, 4])
 def test_cvtColor_both_directions_vs_oracle(ctx, orc, space):
     """cv::cvtColor BGR2{HSV,HLS,Lab,YCrCb} and back, 8UC3: bit-exact against the oracle's restatement (every 8-bit
-    colour of a dense random sample, a real-looking frame, strided batches)."""
+    colour of a dense random sample, a real-looking frame, a contiguous batch of three frames; padded, gapped and
+    misaligned batches are tests/test_layouts_gpu.py's)."""
     rng = np.random.default_rng(space)
     for img in (rng.integers(0, 256, (96, 128, 3), dtype=np.uint8), synth.uw_frame(4, 135, 241)):
         fwd = pp.cvtColor(ctx, _dev(img), space).cpu().numpy()
