@@ -14,8 +14,9 @@
 // --device-jpeg: the enhanced frames of a step are encoded on the device (uwip_jpeg_encode_host on the pipe's context, from
 // the step's frames in the staging area) and the files are written from the returned streams: the same bytes as without it.
 // --device-png: the files are .png, encoded on the device in the same way (uwip_png_encode_host): the pixels of --png, other bytes.
-// --device-decode (.avi, or a list of .jpg files): the compressed frames of a step are decoded on the pipe's context into a
-// device batch (uwip_jpeg_decode_host), uwip_pipe_step runs on the resident frames, and the results leave as streams
+// --device-decode (.avi, or a list of .jpg / .png files): the compressed frames of a step are decoded on the pipe's context
+// into a device batch -- the frames that start with the PNG signature by uwip_png_decode_host, the others by
+// uwip_jpeg_decode_host, a mixed step run by run --, uwip_pipe_step runs on the resident frames, and the results leave as streams
 // (--device-jpeg) or by a plain download; a frame with a negative status is decoded on the host and copied into its slot.
 // The files and both reports are the same bytes as without the flag.  The steps run one after another here (decode, step,
 // wait, results): the overlap of upload, kernels and download that uwip_pipe_step_host gives the raw-frame path is not used.
@@ -39,7 +40,7 @@ int main(int argc, char **argv)
                     "  --guard-s / --min6 / --relative-threshold   the library's opt-in deviations from the reference's rules (uwip.h)\n"
                     "  --device-jpeg   encode the .jpg files on the device (same bytes; ignored with --png)\n"
                     "  --device-png    write .png files encoded on the device (the pixels of --png; the bytes differ)\n"
-                    "  --device-decode decode the input JPEG frames on the device (same files; a frame the device decoder leaves is decoded on the host)\n"
+                    "  --device-decode decode the input JPEG and PNG frames on the device (same files; a frame the device decoder leaves is decoded on the host)\n"
                     "  --keyframes   select key frames as videostrip does (report: <prefix>videostrip_report.txt)\n"
                     "  -k N          frames of the refinement window (default 11)\n"
                     "  -p X          minOverlap (default 0.4)\n"
@@ -153,9 +154,23 @@ int main(int argc, char **argv)
                     jptr[j] = jfiles[j].data(); jlen[j] = jfiles[j].size();
                 }
             }
-            if (uwip_jpeg_decode_host(ctx, jptr.data(), jlen.data(), B, &bin, nullptr, jstatus.data())) {
-                std::printf("uwip_jpeg_decode_host: %s\n", uwip_last_error(ctx));
-                return false;
+            // a step of one kind is one call; a mixed step is split into its runs of one kind, each decoded into its slots
+            static const uint8_t png_sig[8] = {137, 80, 78, 71, 13, 10, 26, 10};
+            auto is_png = [&](int j) { return jlen[j] >= 8 && !std::memcmp(jptr[j], png_sig, 8); };
+            for (int j0 = 0; j0 < B;) {
+                int j1 = j0 + 1;
+                while (j1 < B && is_png(j1) == is_png(j0)) ++j1;
+                uwip_batch_u8 bq = bin;
+                bq.frames = j1 - j0;
+                bq.data = (uint8_t *)d_in + fbytes * j0;
+                const bool png = is_png(j0);
+                const int rcq = png ? uwip_png_decode_host(ctx, jptr.data() + j0, jlen.data() + j0, j1 - j0, &bq, nullptr, jstatus.data() + j0)
+                                    : uwip_jpeg_decode_host(ctx, jptr.data() + j0, jlen.data() + j0, j1 - j0, &bq, nullptr, jstatus.data() + j0);
+                if (rcq) {
+                    std::printf("%s: %s\n", png ? "uwip_png_decode_host" : "uwip_jpeg_decode_host", uwip_last_error(ctx));
+                    return false;
+                }
+                j0 = j1;
             }
             for (int j = 0; j < B; ++j) {
                 if (jstatus[j] == 0) continue;

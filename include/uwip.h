@@ -674,6 +674,48 @@ int uwip_jpeg_decode(uwip_ctx *ctx, const uint8_t *const *h_streams, const size_
 int uwip_jpeg_decode_host(uwip_ctx *ctx, const uint8_t *const *h_streams, const size_t *h_sizes, int n, const uwip_batch_u8 *out,
                           const uwip_jpeg_decode_opts *opts, int32_t *h_status);
 
+/* ---- reading the frames: PNG on the device ---------------------------------------------------------------------------
+ * cv::imread / cv::imdecode of a .png for a batch, on the device (imgio::read_png of cli/imgio.hpp is the host form and the
+ * contract: where the status is 0 the pixels are its pixels byte for byte, and the status is 0 exactly where it returns true
+ * and the size fits).  8 bit, no interlace, colour types 0 / 2 / 4 / 6: alpha is dropped, RGB becomes BGR, grey is replicated
+ * into a 3-channel batch.  Chunk CRCs are not checked (the host reader checks none).  The zlib stream is the concatenation of
+ * the IDAT payloads up to IEND and must pass what zlib's uncompress passes: the header check (method 8, CINFO <= 7, FCHECK, no
+ * FDICT), zlib's rules for sets of code lengths (an over-subscribed set is refused, an incomplete one allowed only as zlib
+ * allows it, the end-of-block code must be present, HLIT <= 286, HDIST <= 30), no distance beyond the bytes already produced,
+ * a final block, the Adler-32, and an inflated length of exactly rows * (1 + cols * samples).  Bytes behind the stream's end
+ * are ignored; a filter type above 4 behaves as type 0, as in the host loop.
+ * uwip_png_info: the chunk walk, the IHDR rules and the zlib header alone (host, pure, no device needed): rows, cols and the
+ *   channels (1 for colour types 0 / 4, 3 for 2 / 6) of a stream read_png would inflate; UWIP_ERR_UNSUPPORTED otherwise
+ *   (palette, other depths, interlace, a chunk that overruns the file, no IDAT ...).
+ * uwip_png_decode: parses the n streams on the host, copies their IDAT payloads through page-locked staging owned by the
+ *   library to the device on the context's stream, queues the kernels and returns without waiting (reuse of the staging
+ *   buffer waits, polling an event, for the previous call's upload only).  `out` is a device batch of n frames with 3 channels
+ *   or 1 channel (grey streams only); any step, frame_stride and alignment.  The workspace is sized from `out` at four
+ *   samples per pixel, never from an IHDR.  d_status[f] (device) is 0 or one of the codes below -- a status, not an error:
+ *   the other frames are complete, and the pixels of a frame with a negative status are unspecified but stay inside its slot.
+ *     UWIP_PNG_BAD_STREAM     read_png returns false
+ *     UWIP_PNG_SIZE_MISMATCH  the IHDR size is not out->rows x out->cols, or a colour stream (types 2 / 6) goes into a
+ *                             1-channel batch
+ *   opts (NULL: the defaults): segmented 1 (and -1, the library's choice) first inflates the segments between the IDAT
+ *   boundaries that follow an empty stored block (00 00 FF FF), one wavefront each, segment i at inflated offset
+ *   i * uwip_png_chunk_bytes(), and accepts a frame only when every segment proves the assumption; every other
+ *   frame, and with segmented 0 every frame, is inflated from its first byte by one wavefront.  The pixels and statuses do not
+ *   depend on it.  d_counts, when not NULL, receives three 64-bit counts on the device: segments accepted from the parallel
+ *   pass, frames that took the serial pass, frames in all.  Without a device the call fails with UWIP_ERR_HIP.
+ * uwip_png_decode_host: the same, waits, and returns the status array in host memory. */
+#define UWIP_PNG_BAD_STREAM    (-1)
+#define UWIP_PNG_SIZE_MISMATCH (-2)
+typedef struct uwip_png_decode_opts {
+    int32_t   segmented;   /* -1 library's choice (= 1), 0 one wavefront per stream only, 1 try IDAT-boundary segments first */
+    int32_t   reserved;    /* 0 */
+    uint64_t *d_counts;    /* may be NULL; device, 3 x u64 */
+} uwip_png_decode_opts;
+int uwip_png_info(const uint8_t *buf, size_t len, int32_t *rows, int32_t *cols, int32_t *channels);
+int uwip_png_decode(uwip_ctx *ctx, const uint8_t *const *h_streams, const size_t *h_sizes, int n, const uwip_batch_u8 *out,
+                    const uwip_png_decode_opts *opts, int32_t *d_status);
+int uwip_png_decode_host(uwip_ctx *ctx, const uint8_t *const *h_streams, const size_t *h_sizes, int n, const uwip_batch_u8 *out,
+                         const uwip_png_decode_opts *opts, int32_t *h_status);
+
 #ifdef __cplusplus
 }
 #endif

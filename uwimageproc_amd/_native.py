@@ -65,6 +65,12 @@ class JpegDecodeOpts(C.Structure):
     _fields_ = [("sync_rounds", C.c_int32), ("reserved", C.c_int32), ("d_unsettled", C.c_void_p)]
 
 
+class PngDecodeOpts(C.Structure):
+    """Mirror of ``uwip_png_decode_opts``."""
+
+    _fields_ = [("segmented", C.c_int32), ("reserved", C.c_int32), ("d_counts", C.c_void_p)]
+
+
 class KeyframeConfig(C.Structure):
     """Mirror of ``uwip_keyframe_config``."""
 
@@ -191,6 +197,9 @@ SIGNATURES = {
     "uwip_jpeg_info": (C.c_int, [_P, C.c_size_t, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "uwip_jpeg_decode": (C.c_int, [_P, _P, _P, C.c_int, _B, _P, _P]),
     "uwip_jpeg_decode_host": (C.c_int, [_P, _P, _P, C.c_int, _B, _P, _P]),
+    "uwip_png_info": (C.c_int, [_P, C.c_size_t, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "uwip_png_decode": (C.c_int, [_P, _P, _P, C.c_int, _B, _P, _P]),
+    "uwip_png_decode_host": (C.c_int, [_P, _P, _P, C.c_int, _B, _P, _P]),
 }
 
 

@@ -110,6 +110,7 @@ UWIP_API int uwip_ctx_destroy(uwip_ctx *ctx)
     for (auto e : ctx->event_pool) (void)hipEventDestroy(e);
     if (ctx->wait_ev) (void)hipEventDestroy(ctx->wait_ev);
     if (ctx->jpd_ev) (void)hipEventDestroy(ctx->jpd_ev);
+    if (ctx->pngd_ev) (void)hipEventDestroy(ctx->pngd_ev);
     for (auto &kv : ctx->ws) if (kv.second.ptr) (void)hipFree(kv.second.ptr);
     for (auto &kv : ctx->hs) if (kv.second.ptr) (void)hipHostFree(kv.second.ptr);
     for (auto &kv : ctx->tables) if (kv.second.ptr) (void)hipFree(kv.second.ptr);

@@ -1,0 +1,574 @@
+// PNG decoding of a batch on the device: imgio::read_png (cli/imgio.hpp, the reader of the CLIs) without the host inflate and
+// without raw pixels on the link.  Where the status is 0 the pixels are the host reader's byte for byte, and the status is 0
+// exactly where the host reader returns true and the size fits.  The chunk walk, the IHDR rules and the zlib header are checked
+// on the host (png_parse.hpp, the host reader's walk); the IDAT payloads and one descriptor per frame and segment are uploaded.
+// The stages, all on the context's stream, none waits for the host:
+//   k_pngd_inflate  one wavefront per segment.  The symbol decode is wave-uniform and serial in the bit stream: every lane
+//                   decodes the same tokens, up to 64 per round, lane i keeps token i in LDS with its output offset (the running
+//                   sum of the token lengths).  Then all lanes write the round: literals by their lanes, matches one after the
+//                   other with the lanes across their bytes (distance < length: a period of `distance`).  A dynamic block's
+//                   tables are built by the lanes into LDS: a direct look-up table for the short codes, first code / count /
+//                   sorted symbols for the rest.  Stored blocks are a copy by all lanes.  Inflated bytes go to the frame's
+//                   workspace; back references read from there.
+//                   Launch 0 decodes the segments the host parse proposed (cuts at IDAT boundaries behind 00 00 FF FF; segment
+//                   i assumed to start at inflated offset i * 32768); launch 1, one wavefront per frame, accepts a frame all of
+//                   whose segments report success and decodes every other frame again from its first byte.
+//   k_pngd_adler    (a, b) sums of every 32 KiB piece of the inflated bytes, 128 bytes per thread;
+//   k_pngd_unfilter one wavefront per frame: the pieces' sums into the Adler-32 and its comparison with the stream's (a
+//                   mismatch is UWIP_PNG_BAD_STREAM), then the row filters undone in place, 64 rows at a time on the diagonal:
+//                   lane L has row r0 + L and is one pixel behind lane L - 1, whose last result (through LDS) is "up", whose
+//                   result before that "upper left"; the band's first row reads the row above from memory;
+//   k_pngd_color    one thread per pixel: the type byte and alpha dropped, RGB -> BGR or grey replicated, the caller's layout.
+// What bounds the inflate loop on untrusted bytes: the bit position may not pass the segment's length (bits behind it read as
+// zeros without a load, and the first step that passes it ends the segment); every store is checked against the segment's
+// window before its token is taken; table indices are masked, or below a symbol count by construction; a round consumes at
+// least one bit or ends the segment.
+#include "uwip_internal.hpp"
+#include "device_utils.hpp"
+#include "inflate_core.hpp"
+#include "png_parse.hpp"
+#include <cstring>
+
+namespace {
+
+using namespace uwip_inflate;
+using uwip_png::kAdlerMod;
+using uwip_png::kChunk;
+
+constexpr int kLLBits = 10, kDBits = 8, kCLBits = 7;     // look-up widths: literal/length, distance, code length codes
+constexpr int kRound = 64;                               // tokens per round: one per lane
+constexpr int kBand = 64;                                // rows per pass of the unfilter: one per lane
+constexpr int kPngBad = -1;                              // UWIP_PNG_BAD_STREAM
+
+struct PFrame {                 // per frame, from the host parse
+    int32_t status, spp;
+    uint32_t zoff, zlen;        // its zlib stream in the uploaded bytes
+    uint32_t seg0, nseg;        // its segments of launch 0 (nseg 0: none, launch 1 decodes it)
+    uint32_t pad[2];
+};
+struct PSeg { uint32_t frame, idx, off, len; };          // input bytes [off, off + len) of the frame's stream
+struct PRes { uint32_t ok, adler_pos, maxdist, pad; };   // per segment, then per frame: adler_pos in the frame's stream
+struct PGeoD { int rows, cols; uint32_t ws_stride, npieces; };
+
+struct PBufs {
+    const PFrame *fr;
+    const PSeg *seg;
+    const uint8_t *src;
+    uint8_t *ws;                // per frame ws_stride bytes: the inflated bytes, unfiltered in place
+    PRes *res;                  // [nsegtot + frames]
+    uint32_t *asum;             // [frames][npieces][2]
+    int32_t *status;
+    unsigned long long *counts; // segments accepted in launch 0, frames launch 1 decoded, frames
+    uint32_t nsegtot, nframes;
+};
+
+__device__ __forceinline__ uint32_t frame_total(const PGeoD &g, int spp) { return (uint32_t)g.rows * (1u + (uint32_t)g.cols * (uint32_t)spp); }
+
+// 32 bits of the segment from bit p on, least significant first; bits at or past its last byte are zeros (no load there).
+// The second word may lie behind the segment: the buffer is 16 bytes longer than its last stream.
+__device__ __forceinline__ uint32_t peek32(const uint8_t *src, uint32_t a0, uint32_t len, uint32_t p)
+{
+    const uint32_t by = p >> 3;
+    if (by >= len) return 0u;
+    const uint32_t a = a0 + by;
+    const uint32_t *w = reinterpret_cast<const uint32_t *>(src) + (a >> 2);
+    const uint64_t x = (uint64_t)w[0] | ((uint64_t)w[1] << 32);
+    uint32_t v = (uint32_t)(x >> ((a & 3u) * 8u + (p & 7u)));
+    const uint32_t rem = len * 8u - p;                       // >= 1
+    if (rem < 32u) v &= (1u << rem) - 1u;
+    return v;
+}
+
+struct Tables {
+    uint16_t ll[1 << kLLBits], d[1 << kDBits], cl[1 << kCLBits];
+    uint16_t ll_sorted[kFixedLL], d_sorted[kFixedDist], cl_sorted[uwip_png::kNumCL];
+    CodeSet ll_set, d_set, cl_set;
+    uint8_t lens[kFixedLL + kFixedDist], cl_lens[uwip_png::kNumCL + 1];
+    uint16_t tlen[kRound], tval[kRound];                     // a round's tokens: length (1: a literal), byte or distance
+    uint32_t tout[kRound];                                   // where each goes, from the segment's first byte
+    uint32_t bad;
+};
+
+// The lanes build the decoding tables of n code lengths (each 0..15): false where zlib refuses the set.
+__device__ bool build_table(const uint8_t *lens, int n, int kind, int lutbits, uint16_t *lut, uint16_t *sorted, CodeSet &c)
+{
+    const int lane = (int)threadIdx.x;
+    if (lane < 16) c.cnt[lane] = 0u;
+    for (int i = lane; i < (1 << lutbits); i += 64) lut[i] = 0;
+    __syncthreads();
+    for (int i = lane; i < n; i += 64) if (lens[i]) atomicAdd(&c.cnt[lens[i] & 15], 1u);
+    __syncthreads();
+    if (!code_set_accepted(c.cnt, kind)) return false;       // the same answer in every lane
+    if (lane == 0) code_set_first(c);
+    __syncthreads();
+    if (lane >= 1 && lane <= kMaxBits && c.cnt[lane]) {      // lane l deals out the codes of length l in symbol order
+        const uint32_t l = (uint32_t)lane;
+        uint32_t code = c.first[l], at = c.off[l];
+        for (int s = 0; s < n; ++s) {
+            if (lens[s] != l) continue;
+            sorted[at++] = (uint16_t)s;                      // at < off[l] + cnt[l] <= n
+            if ((int)l <= lutbits)
+                for (uint32_t k = rev_bits(code, (int)l); k < (1u << lutbits); k += 1u << l) lut[k] = lut_entry((uint32_t)s, l);
+            ++code;
+        }
+    }
+    __syncthreads();
+    return true;
+}
+
+__device__ __forceinline__ bool decode_sym(const uint16_t *lut, int lutbits, const CodeSet &c, const uint16_t *sorted, uint32_t v,
+                                           uint32_t &len, uint32_t &sym)
+{
+    const uint32_t e = lut[v & ((1u << lutbits) - 1u)];
+    if (e) { len = e >> 12; sym = e & 0xFFFu; return true; }
+    return decode_slow(c, sorted, lutbits, v, len, sym);
+}
+
+// a dynamic block's header from bit pos on: the code lengths into T.lens and the two tables; false: zlib refuses it (or the
+// segment ends inside it)
+__device__ bool dynamic_header(Tables &T, const uint8_t *src, uint32_t a0, uint32_t len, uint32_t &pos)
+{
+    const uint32_t lane = threadIdx.x, lenbits = len * 8u;
+    uint32_t v = peek32(src, a0, len, pos);
+    const uint32_t nlen = (v & 31u) + 257u, nd = ((v >> 5) & 31u) + 1u, nc = ((v >> 10) & 15u) + 4u;
+    pos += 14u;
+    if (pos > lenbits || nlen > (uint32_t)kMaxLL || nd > (uint32_t)kMaxDist) return false;
+    if (lane < (uint32_t)uwip_png::kNumCL) T.cl_lens[lane] = 0;
+    __syncthreads();
+    for (uint32_t i = 0; i < nc; ++i) {                       // nc <= 19
+        const uint32_t val = peek32(src, a0, len, pos) & 7u;
+        pos += 3u;
+        if (lane == 0) T.cl_lens[cl_order((int)i)] = (uint8_t)val;
+    }
+    if (pos > lenbits) return false;
+    __syncthreads();
+    if (!build_table(T.cl_lens, uwip_png::kNumCL, kCodes, kCLBits, T.cl, T.cl_sorted, T.cl_set)) return false;
+    const uint32_t want = nlen + nd;                          // <= 316
+    uint32_t have = 0, prev = 0;
+    while (have < want) {
+        v = peek32(src, a0, len, pos);
+        const uint32_t e = T.cl[v & ((1u << kCLBits) - 1u)];  // every code of this set has at most 7 bits
+        if (!e) return false;
+        const uint32_t l = e >> 12, sym = e & 0xFFFu;
+        pos += l;
+        if (sym < 16u) {
+            if (lane == 0) T.lens[have] = (uint8_t)sym;
+            prev = sym; ++have;
+        } else {
+            uint32_t rep, val = 0;
+            if (sym == 16u) { if (have == 0u) return false; rep = 3u + ((v >> l) & 3u); pos += 2u; val = prev; }
+            else if (sym == 17u) { rep = 3u + ((v >> l) & 7u); pos += 3u; }
+            else { rep = 11u + ((v >> l) & 127u); pos += 7u; }
+            if (have + rep > want) return false;
+            for (uint32_t j = lane; j < rep; j += 64u) T.lens[have + j] = (uint8_t)val;
+            have += rep; prev = val;
+        }
+        if (pos > lenbits) return false;
+    }
+    __syncthreads();
+    if (T.lens[256] == 0) return false;                       // no end-of-block code
+    if (!build_table(T.lens, (int)nlen, kLens, kLLBits, T.ll, T.ll_sorted, T.ll_set)) return false;
+    return build_table(T.lens + nlen, (int)nd, kDists, kDBits, T.d, T.d_sorted, T.d_set);
+}
+
+// pass 0: block s is segment s.  pass 1: block f is frame f -- accepted from its segments, or decoded again as a whole.
+__global__ __launch_bounds__(64) void k_pngd_inflate(PBufs B, PGeoD g, int pass)
+{
+    __shared__ Tables T;
+    const uint32_t lane = threadIdx.x;
+    uint32_t f, a0, len, win, rslot;
+    uint8_t *out;
+    bool lastseg;
+    if (pass == 0) {
+        const PSeg sg = B.seg[blockIdx.x];
+        f = sg.frame;
+        const PFrame fr = B.fr[f];
+        const uint32_t total = frame_total(g, fr.spp), base = sg.idx * (uint32_t)kChunk;
+        rslot = blockIdx.x;
+        lastseg = sg.idx + 1u == fr.nseg;
+        if ((uint64_t)sg.idx * (uint64_t)kChunk > (uint64_t)total) {                                   // its window lies behind the frame: refused
+            if (lane == 0) B.res[rslot] = PRes{0u, 0u, 0u, 0u};
+            return;
+        }
+        a0 = fr.zoff + sg.off; len = sg.len;
+        win = lastseg ? total - base : min((uint32_t)kChunk, total - base);
+        out = B.ws + (size_t)f * g.ws_stride + base;
+    } else {
+        f = blockIdx.x;
+        const PFrame fr = B.fr[f];
+        rslot = B.nsegtot + f;
+        if (f == 0u && lane == 0u) B.counts[2] = B.nframes;
+        if (fr.status != 0) {
+            if (lane == 0) { B.status[f] = fr.status; B.res[rslot] = PRes{0u, 0u, 0u, 0u}; }
+            return;
+        }
+        if (fr.nseg) {
+            if (lane == 0) T.bad = 0u;
+            __syncthreads();
+            uint32_t nb = 0;
+            for (uint32_t s = lane; s < fr.nseg; s += 64u) nb += B.res[fr.seg0 + s].ok ? 0u : 1u;
+            if (nb) atomicAdd(&T.bad, nb);
+            __syncthreads();
+            const uint32_t bad = T.bad;
+            if (bad == 0u || fr.nseg == 1u) {                 // one segment is the whole stream: its answer stands
+                if (lane == 0) {
+                    B.status[f] = bad ? kPngBad : 0;
+                    B.res[rslot] = B.res[fr.seg0 + fr.nseg - 1u];
+                }
+                return;
+            }
+        }
+        if (lane == 0) atomicAdd(&B.counts[1], 1ull);
+        a0 = fr.zoff + 2u; len = fr.zlen - 2u;                // zlen >= 2: the host parse read the zlib header
+        win = frame_total(g, fr.spp);
+        out = B.ws + (size_t)f * g.ws_stride;
+        lastseg = true;
+    }
+    const uint8_t *src = B.src;
+    const uint32_t lenbits = len * 8u;
+    uint32_t pos = 0, o = 0, maxd = 0, adler_pos = 0;
+    bool fail = false, done = false, in_block = false, final_blk = false, last_empty = false;
+    while (!done && !fail) {
+        bool block_end = false;
+        if (!in_block) {
+            uint32_t v = peek32(src, a0, len, pos);
+            final_blk = v & 1u;
+            const uint32_t type = (v >> 1) & 3u;
+            pos += 3u;
+            if (pos > lenbits) { fail = true; break; }
+            if (type == 0u) {
+                pos = (pos + 7u) & ~7u;
+                if (pos + 32u > lenbits) { fail = true; break; }
+                v = peek32(src, a0, len, pos);
+                const uint32_t L = v & 0xFFFFu;
+                pos += 32u;
+                const uint32_t by = pos >> 3;
+                if ((L ^ 0xFFFFu) != (v >> 16) || L > len - by || L > win - o) { fail = true; break; }
+                for (uint32_t j = lane; j < L; j += 64u) out[o + j] = src[a0 + by + j];
+                o += L; pos += L * 8u;
+                __syncthreads();
+                last_empty = L == 0u;
+                block_end = true;
+            } else if (type == 1u) {
+                for (uint32_t i = lane; i < (uint32_t)(kFixedLL + kFixedDist); i += 64u) T.lens[i] = (uint8_t)fixed_len((int)i);
+                __syncthreads();
+                build_table(T.lens, kFixedLL, kLens, kLLBits, T.ll, T.ll_sorted, T.ll_set);
+                build_table(T.lens + kFixedLL, kFixedDist, kDists, kDBits, T.d, T.d_sorted, T.d_set);
+                in_block = true;
+            } else if (type == 2u) {
+                if (!dynamic_header(T, src, a0, len, pos)) { fail = true; break; }
+                in_block = true;
+            } else { fail = true; break; }
+        } else {
+            // a round: up to 64 tokens, every lane decodes them all and keeps its own
+            uint32_t ntok = 0, o_r = o;
+            bool eob = false;
+            while (ntok < (uint32_t)kRound) {
+                uint32_t v = peek32(src, a0, len, pos), l, sym;
+                if (!decode_sym(T.ll, kLLBits, T.ll_set, T.ll_sorted, v, l, sym)) { fail = true; break; }
+                pos += l;
+                if (sym < 256u) {
+                    if (o_r >= win) { fail = true; break; }
+                    if (lane == ntok) { T.tlen[lane] = 1; T.tval[lane] = (uint16_t)sym; T.tout[lane] = o_r; }
+                    ++ntok; ++o_r;
+                } else if (sym == 256u) { eob = true; break; }
+                else {
+                    if (sym >= (uint32_t)kMaxLL) { fail = true; break; }
+                    const uint32_t idx = sym - 257u, eb = length_extra(idx);
+                    const uint32_t mlen = length_base(idx) + ((v >> l) & ((1u << eb) - 1u));      // l + eb <= 20 bits of v
+                    pos += eb;
+                    v = peek32(src, a0, len, pos);
+                    uint32_t l2, dsym;
+                    if (!decode_sym(T.d, kDBits, T.d_set, T.d_sorted, v, l2, dsym) || dsym >= (uint32_t)kMaxDist) { fail = true; break; }
+                    const uint32_t de = dist_extra(dsym), dist = dist_base(dsym) + ((v >> l2) & ((1u << de) - 1u));   // l2 + de <= 28
+                    pos += l2 + de;
+                    // a distance beyond the segment's own bytes: before the stream (bad), or into another segment's window
+                    if (dist > o_r || mlen > win - o_r) { fail = true; break; }
+                    maxd = max(maxd, dist);
+                    if (lane == ntok) { T.tlen[lane] = (uint16_t)mlen; T.tval[lane] = (uint16_t)dist; T.tout[lane] = o_r; }
+                    ++ntok; o_r += mlen;
+                }
+                if (pos > lenbits) { fail = true; break; }
+            }
+            if (pos > lenbits) fail = true;
+            if (fail) break;
+            __syncthreads();
+            // the round's bytes: literals first, then the matches in order; a match whose source may hold bytes of a match
+            // written since the last barrier waits for them
+            if (lane < ntok && T.tlen[lane] == 1) out[T.tout[lane]] = (uint8_t)T.tval[lane];
+            __syncthreads();
+            uint32_t dirty = 0xFFFFFFFFu;
+            for (uint32_t i = 0; i < ntok; ++i) {
+                const uint32_t ml = T.tlen[i];
+                if (ml == 1u) continue;
+                const uint32_t dist = T.tval[i], to = T.tout[i], s0 = to - dist;
+                if (s0 + min(ml, dist) > dirty) { __syncthreads(); dirty = 0xFFFFFFFFu; }
+                for (uint32_t j = lane; j < ml; j += 64u) out[to + j] = out[s0 + (dist >= ml ? j : j % dist)];
+                dirty = min(dirty, to);
+            }
+            __syncthreads();
+            o = o_r;
+            if (eob) { block_end = true; in_block = false; last_empty = false; }
+        }
+        if (block_end) {
+            if (final_blk) {
+                pos = (pos + 7u) & ~7u;
+                adler_pos = pos >> 3;
+                if (!lastseg || adler_pos + 4u > len) fail = true;            // the Adler-32 follows the last block
+                done = true;
+            } else if (!lastseg && pos == lenbits) {                          // the segment's input ends here
+                if (!last_empty) fail = true;
+                done = true;
+            }
+        }
+    }
+    const bool ok = !fail && o == win;
+    if (lane == 0) {
+        B.res[rslot] = PRes{ok ? 1u : 0u, a0 - B.fr[f].zoff + adler_pos, maxd, 0u};
+        if (pass == 0) { if (ok) atomicAdd(&B.counts[0], 1ull); }
+        else B.status[f] = ok ? 0 : kPngBad;
+    }
+}
+
+__global__ __launch_bounds__(256) void k_pngd_adler(PBufs B, PGeoD g)
+{
+    __shared__ uint32_t s_scan[8];
+    const int f = blockIdx.y, t = threadIdx.x;
+    if (B.status[f] != 0) return;
+    const uint32_t total = frame_total(g, B.fr[f].spp), base = blockIdx.x * (uint32_t)kChunk;
+    if (base >= total) return;
+    const int n = (int)min((uint32_t)kChunk, total - base);
+    const uint8_t *d = B.ws + (size_t)f * g.ws_stride + base;
+    const int b0 = min(t * (kChunk / 256), n), b1 = min(b0 + kChunk / 256, n);
+    uint32_t sa = 0, sb = 0;
+    for (int p = b0; p < b1; ++p) { sa += d[p]; sb += (uint32_t)(n - p) * d[p]; }          // < 128 * 32768 * 255
+    const uint32_t a = block256_sum_u32(sa % kAdlerMod, s_scan) % kAdlerMod;
+    const uint32_t b = block256_sum_u32(sb % kAdlerMod, s_scan) % kAdlerMod;
+    if (t == 0) { uint32_t *q = B.asum + ((size_t)f * g.npieces + blockIdx.x) * 2; q[0] = a; q[1] = b; }
+}
+
+__global__ __launch_bounds__(64) void k_pngd_unfilter(PBufs B, PGeoD g)
+{
+    __shared__ uint32_t s_px[2][kBand];
+    __shared__ uint32_t s_bad;
+    const int f = blockIdx.x, lane = threadIdx.x;
+    if (B.status[f] != 0) return;
+    const PFrame fr = B.fr[f];
+    const int spp = fr.spp, rows = g.rows, cols = g.cols;
+    const uint32_t total = frame_total(g, spp);
+    if (lane == 0) {
+        uint32_t A = 1, Bs = 0;
+        for (uint32_t p = 0; p * (uint32_t)kChunk < total; ++p) {
+            const uint32_t *q = B.asum + ((size_t)f * g.npieces + p) * 2;
+            uwip_png::adler_append(A, Bs, q[0], q[1], min((uint32_t)kChunk, total - p * (uint32_t)kChunk));
+        }
+        const uint8_t *z = B.src + fr.zoff + B.res[B.nsegtot + f].adler_pos;       // four bytes inside the stream (checked)
+        const uint32_t stored = ((uint32_t)z[0] << 24) | ((uint32_t)z[1] << 16) | ((uint32_t)z[2] << 8) | z[3];
+        s_bad = stored != ((Bs << 16) | A);
+    }
+    __syncthreads();
+    if (s_bad) {                                                                   // written behind the barrier: every lane has read it
+        if (lane == 0) B.status[f] = kPngBad;
+        return;
+    }
+    uint8_t *ws = B.ws + (size_t)f * g.ws_stride;
+    const size_t rstride = (size_t)cols * spp + 1;
+    for (int r0 = 0; r0 < rows; r0 += kBand) {
+        const int y = r0 + lane;
+        const bool active = y < rows;
+        uint8_t *row = ws + (size_t)(active ? y : 0) * rstride + 1;
+        int ft = active ? row[-1] : 0;
+        if (ft > 4) ft = 0;                                                        // the host loop's default
+        const uint8_t *up = (lane == 0 && r0 > 0) ? row - rstride : nullptr;
+        uint32_t a = 0, c = 0;                                                     // the pixel to the left, the one above it
+        const int nsteps = cols + min(kBand, rows - r0) - 1;
+        for (int s = 0; s < nsteps; ++s) {
+            const int x = s - lane;
+            uint32_t res = 0;
+            if (active && x >= 0 && x < cols) {
+                uint32_t b = 0;
+                if (lane > 0) b = s_px[(s - 1) & 1][lane - 1];
+                else if (up) for (int k = 0; k < spp; ++k) b |= (uint32_t)up[(size_t)x * spp + k] << (8 * k);
+                for (int k = 0; k < spp; ++k) {
+                    const int av = (a >> (8 * k)) & 255, bv = (b >> (8 * k)) & 255, cv = (c >> (8 * k)) & 255;
+                    int v = row[(size_t)x * spp + k];
+                    v += ft == 1 ? av : ft == 2 ? bv : ft == 3 ? (av + bv) >> 1 : ft == 4 ? uwip_png::paeth(av, bv, cv) : 0;
+                    row[(size_t)x * spp + k] = (uint8_t)v;
+                    res |= (uint32_t)(v & 255) << (8 * k);
+                }
+                a = res; c = b;
+            }
+            s_px[s & 1][lane] = res;
+            __syncthreads();
+        }
+    }
+}
+
+__global__ __launch_bounds__(256) void k_pngd_color(PBufs B, PGeoD g, uint8_t *out, size_t step, size_t fs, int channels)
+{
+    const int f = blockIdx.y;
+    if (B.status[f] != 0) return;
+    const uint32_t q = blockIdx.x * 256u + threadIdx.x;
+    if (q >= (uint32_t)g.rows * (uint32_t)g.cols) return;
+    const int spp = B.fr[f].spp;
+    const uint32_t y = q / (uint32_t)g.cols, x = q - y * (uint32_t)g.cols;
+    const uint8_t *s = B.ws + (size_t)f * g.ws_stride + (size_t)y * ((size_t)g.cols * spp + 1) + 1 + (size_t)x * spp;
+    uint8_t *p = out + (size_t)f * fs + (size_t)y * step + (size_t)x * channels;
+    if (channels == 1) p[0] = s[0];                                                // grey streams only (the host's rule)
+    else if (spp <= 2) p[0] = p[1] = p[2] = s[0];
+    else { p[0] = s[2]; p[1] = s[1]; p[2] = s[0]; }
+}
+
+// ---- the host side ----------------------------------------------------------------------------------------------------------
+struct PPlan {
+    size_t src_bytes = 0, nseg = 0;
+    bool too_large = false;
+};
+
+// the per-frame workspace comes from the batch's geometry at four samples per pixel, never from an IHDR
+size_t ws_bytes(int rows, int cols) { return (((size_t)rows * ((size_t)cols * 4 + 1)) + 15) & ~(size_t)15; }
+
+// a frame's descriptor and segments from its parse; segmented: one segment per proposed cut and one behind the last
+void plan_frame(PFrame &d, const uwip_pngd::Parsed &p, int rows, int cols, int segmented, std::vector<PSeg> &segs, int f, PPlan &pl)
+{
+    d.zoff = (uint32_t)pl.src_bytes; d.zlen = (uint32_t)p.zlen;
+    pl.src_bytes += (p.zlen + 31) & ~(size_t)15;
+    d.seg0 = (uint32_t)segs.size(); d.nseg = 0;
+    if (segmented) {
+        size_t at = 2;
+        uint32_t i = 0;
+        for (size_t c : p.cuts) { segs.push_back(PSeg{(uint32_t)f, i++, (uint32_t)at, (uint32_t)(c - at)}); at = c; }
+        segs.push_back(PSeg{(uint32_t)f, i++, (uint32_t)at, (uint32_t)(p.zlen - at)});
+        d.nseg = i;
+    }
+    if (pl.src_bytes >= ((size_t)1 << 31)) pl.too_large = true;
+}
+
+}  // namespace
+
+UWIP_API int uwip_png_info(const uint8_t *buf, size_t len, int32_t *rows, int32_t *cols, int32_t *channels)
+{
+    if (!buf || !rows || !cols || !channels) return UWIP_ERR_INVALID;
+    int r = 0, c = 0, ch = 0;
+    if (uwip_pngd::info(buf, len, &r, &c, &ch) != uwip_pngd::PARSE_OK) return UWIP_ERR_UNSUPPORTED;
+    *rows = r; *cols = c; *channels = ch;
+    return UWIP_OK;
+}
+
+UWIP_API int uwip_png_decode(uwip_ctx *ctx, const uint8_t *const *h_streams, const size_t *h_sizes, int n, const uwip_batch_u8 *out,
+                             const uwip_png_decode_opts *opts, int32_t *d_status)
+{
+    if (!ctx) {                                               // no context: because there is no device, or a plain bad argument
+        int ndev = 0;
+        return (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) ? UWIP_ERR_HIP : UWIP_ERR_INVALID;
+    }
+    int rc = uwip_check_batch(ctx, out, 0);
+    if (rc) return rc;
+    UWIP_REQUIRE(ctx, n >= 0 && n <= 65535, "at most 65535 frames per call");
+    UWIP_REQUIRE(ctx, out->frames == n, "the batch must hold one frame per stream");
+    UWIP_REQUIRE(ctx, !opts || (opts->segmented >= -1 && opts->segmented <= 1 && opts->reserved == 0), "segmented must be -1, 0 or 1");
+    if (n == 0) return UWIP_OK;
+    UWIP_REQUIRE(ctx, h_streams != nullptr && h_sizes != nullptr && d_status != nullptr, "null argument");
+    UWIP_REQUIRE(ctx, out->rows >= 1 && out->cols >= 1, "empty frame");
+    UWIP_REQUIRE(ctx, out->rows <= 65535 && out->cols <= 65535, "at most 65535 rows / columns");
+    for (int f = 0; f < n; ++f) UWIP_REQUIRE(ctx, h_streams[f] != nullptr || h_sizes[f] == 0, "null stream");
+    for (int f = 0; f < n; ++f) UWIP_REQUIRE(ctx, h_sizes[f] < ((size_t)1 << 28), "a stream of 256 MiB or more");
+    const int segmented = (opts && opts->segmented == 0) ? 0 : 1;
+    const size_t wsb = ws_bytes(out->rows, out->cols);
+    UWIP_REQUIRE(ctx, wsb < ((size_t)1 << 31), "frame too large");
+
+    std::vector<uwip_pngd::Parsed> parsed((size_t)n);
+    std::vector<PFrame> fr((size_t)n);
+    std::vector<PSeg> segs;
+    PPlan pl;
+    for (int f = 0; f < n; ++f) {
+        PFrame &d = fr[f];
+        std::memset(&d, 0, sizeof d);
+        uwip_pngd::Parsed &p = parsed[f];
+        d.status = uwip_pngd::parse(h_streams[f], h_sizes[f], p);
+        if (d.status == 0 && ((int64_t)p.H != out->rows || (int64_t)p.W != out->cols || (p.spp >= 3 && out->channels == 1)))
+            d.status = UWIP_PNG_SIZE_MISMATCH;
+        d.spp = d.status == 0 ? p.spp : 1;
+        if (d.status == 0) plan_frame(d, p, out->rows, out->cols, segmented, segs, f, pl);
+    }
+    UWIP_REQUIRE(ctx, !pl.too_large && segs.size() < ((size_t)1 << 24), "batch too large for one call");
+
+    // The page-locked staging buffer holds the descriptors, the segments, then the zlib streams.  It is free again once the
+    // previous call's upload has finished: poll that event (the stream is not drained) before the buffer is touched.
+    static_assert(sizeof(PFrame) % 16 == 0 && sizeof(PSeg) == 16, "the streams follow the descriptors at a 16-byte boundary");
+    if (!ctx->pngd_ev) UWIP_HIP(ctx, hipEventCreateWithFlags(&ctx->pngd_ev, hipEventDisableTiming));
+    else UWIP_HIP(ctx, uwip_event_wait(ctx->pngd_ev, 200));
+    const size_t nsegtot = segs.size(), hdr = (size_t)n * sizeof(PFrame) + nsegtot * sizeof(PSeg);
+    const size_t in_bytes = hdr + pl.src_bytes + 16;
+    uint8_t *h_in = static_cast<uint8_t *>(uwip_host_ws(ctx, "pngdec.in", in_bytes));
+    if (!h_in) return UWIP_ERR_NOMEM;
+    std::memcpy(h_in, fr.data(), (size_t)n * sizeof(PFrame));
+    if (nsegtot) std::memcpy(h_in + (size_t)n * sizeof(PFrame), segs.data(), nsegtot * sizeof(PSeg));
+    for (int f = 0; f < n; ++f)
+        if (fr[f].status == 0) uwip_pngd::gather(h_streams[f], parsed[f], h_in + hdr + fr[f].zoff);
+    std::memset(h_in + hdr + pl.src_bytes, 0, 16);
+
+    const uint32_t npieces = (uint32_t)((wsb + kChunk - 1) / kChunk);
+    uint8_t *d_in = static_cast<uint8_t *>(uwip_ws(ctx, "pngdec.in", in_bytes));
+    uint8_t *ws = static_cast<uint8_t *>(uwip_ws(ctx, "pngdec.inflated", (size_t)n * wsb + 16));
+    // the small arrays share one buffer: the counts, the results, the Adler sums
+    uint64_t *meta = static_cast<uint64_t *>(uwip_ws(ctx, "pngdec.meta", 32 + (nsegtot + n) * sizeof(PRes) + (size_t)n * npieces * 8));
+    if (!d_in || !ws || !meta) return UWIP_ERR_NOMEM;
+    UWIP_HIP(ctx, hipMemcpyAsync(d_in, h_in, in_bytes, hipMemcpyHostToDevice, ctx->stream));
+    UWIP_HIP(ctx, hipEventRecord(ctx->pngd_ev, ctx->stream));
+
+    PBufs B;
+    B.fr = reinterpret_cast<const PFrame *>(d_in);
+    B.seg = reinterpret_cast<const PSeg *>(d_in + (size_t)n * sizeof(PFrame));
+    B.src = d_in + hdr;
+    B.ws = ws;
+    B.counts = reinterpret_cast<unsigned long long *>(meta);
+    B.res = reinterpret_cast<PRes *>(meta + 4);
+    B.asum = reinterpret_cast<uint32_t *>(B.res + nsegtot + n);
+    B.status = d_status;
+    B.nsegtot = (uint32_t)nsegtot; B.nframes = (uint32_t)n;
+    PGeoD g;
+    g.rows = out->rows; g.cols = out->cols; g.ws_stride = (uint32_t)wsb; g.npieces = npieces;
+    UWIP_HIP(ctx, hipMemsetAsync(meta, 0, 32, ctx->stream));
+    if (nsegtot) {
+        uwip_kscope ks(ctx, "k_pngd_inflate_segments");
+        k_pngd_inflate<<<(unsigned)nsegtot, 64, 0, ctx->stream>>>(B, g, 0);
+    }
+    {
+        uwip_kscope ks(ctx, "k_pngd_inflate");
+        k_pngd_inflate<<<n, 64, 0, ctx->stream>>>(B, g, 1);
+    }
+    {
+        uwip_kscope ks(ctx, "k_pngd_adler");
+        k_pngd_adler<<<dim3(npieces, n), 256, 0, ctx->stream>>>(B, g);
+    }
+    {
+        uwip_kscope ks(ctx, "k_pngd_unfilter");
+        k_pngd_unfilter<<<n, 64, 0, ctx->stream>>>(B, g);
+    }
+    {
+        uwip_kscope ks(ctx, "k_pngd_color");
+        k_pngd_color<<<dim3(uwip_cdiv((size_t)out->rows * out->cols, 256), n), 256, 0, ctx->stream>>>(
+            B, g, static_cast<uint8_t *>(out->data), out->step, out->frame_stride, out->channels);
+    }
+    if (opts && opts->d_counts)
+        UWIP_HIP(ctx, hipMemcpyAsync(opts->d_counts, B.counts, 24, hipMemcpyDeviceToDevice, ctx->stream));
+    UWIP_HIP(ctx, hipGetLastError());
+    return UWIP_OK;
+}
+
+UWIP_API int uwip_png_decode_host(uwip_ctx *ctx, const uint8_t *const *h_streams, const size_t *h_sizes, int n, const uwip_batch_u8 *out,
+                                  const uwip_png_decode_opts *opts, int32_t *h_status)
+{
+    if (!ctx) return uwip_png_decode(ctx, h_streams, h_sizes, n, out, opts, nullptr);
+    if (int rc = uwip_enter(ctx)) return rc;
+    UWIP_REQUIRE(ctx, n >= 0 && (h_status != nullptr || n == 0), "null status");
+    if (n == 0) return UWIP_OK;
+    int32_t *d_status = static_cast<int32_t *>(uwip_ws(ctx, "pngdec.status", (size_t)n * sizeof(int32_t)));
+    if (!d_status) return UWIP_ERR_NOMEM;
+    int rc = uwip_png_decode(ctx, h_streams, h_sizes, n, out, opts, d_status);
+    if (rc) return rc;
+    UWIP_HIP(ctx, hipMemcpyAsync(h_status, d_status, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+    UWIP_HIP(ctx, uwip_stream_wait(ctx));
+    return UWIP_OK;
+}

@@ -61,6 +61,7 @@ struct uwip_ctx {
     hipEvent_t wait_ev = nullptr;
     // uwip_jpeg_decode: recorded behind the upload out of the page-locked staging buffer, polled before the next call refills it
     hipEvent_t jpd_ev = nullptr;
+    hipEvent_t pngd_ev = nullptr;               // the same for uwip_png_decode's staging buffer
     bool spin_wait = false;
 
     int fail(int code, const char *what, const char *detail = nullptr)

@@ -1,9 +1,11 @@
-"""cv2.imwrite(".png") / cv2.imencode(".png") for a batch, on the device (uwip_png_encode, include/uwip.h).
+"""cv2.imwrite(".png") / cv2.imencode(".png") and cv2.imdecode for a batch, on the device (uwip_png_encode / uwip_png_decode,
+include/uwip.h).
 
 The streams are lossless PNG -- colour type 2 for BGR frames (RGB in the file), 0 for grey ones, adaptive row filters, a
 deflate of runs and per-chunk Huffman codes -- whose pixels are the input's; the bytes are neither OpenCV's nor cli/imgio.hpp's.
-No compute happens here and there is no CPU path: the frames are a device tensor and the kernels of csrc/png_encode.hip do the
-work.
+Decoding returns the pixels of the CLIs' host reader (imgio::read_png, cli/imgio.hpp) for 8-bit non-interlaced grey, grey +
+alpha, RGB and RGBA streams of any encoder.  No compute happens here and there is no CPU path: the frames are a device tensor
+and the kernels of csrc/png_encode.hip and csrc/png_decode.hip do the work.
 """
 from __future__ import annotations
 
@@ -64,3 +66,72 @@ def encode(ctx: Context, frames, filter: int = -1) -> List[bytes]:
         ctx.sync()
         n = sizes.cpu().tolist()
     return [streams[f, : n[f]].cpu().numpy().tobytes() for f in range(len(n))]
+
+
+# ---- decoding (uwip_png_decode, csrc/png_decode.hip) -----------------------------------------------------------------------
+BAD_STREAM, SIZE_MISMATCH = -1, -2
+
+
+def info(stream: bytes) -> Tuple[int, int, int]:
+    """``(rows, cols, channels)`` of a PNG stream the host reader would inflate (``uwip_png_info``; host only); channels is 1
+    for grey and grey + alpha, 3 for RGB and RGBA.  Raises ``UwipError`` for anything else (palette, 16 bit, interlaced,
+    truncated chunks, not a PNG ...)."""
+    r, c, ch = C.c_int32(0), C.c_int32(0), C.c_int32(0)
+    buf = (C.c_uint8 * max(len(stream), 1)).from_buffer_copy(bytes(stream) or b"\0")
+    rc = lib().uwip_png_info(C.cast(buf, _P), len(stream), C.byref(r), C.byref(c), C.byref(ch))
+    if rc != 0:
+        raise UwipError(rc, "not a PNG stream the decoder reads")
+    return r.value, c.value, ch.value
+
+
+def decode_into(ctx: Context, streams: List[bytes], out, segmented: int = -1, counts=None):
+    """Decodes ``streams`` into the device tensor ``out`` (``[F, H, W, 3]`` BGR or ``[F, H, W]`` grey, any strides with packed
+    pixels); returns the int32 device tensor of per-frame statuses.  ``counts``: an int64 device tensor of 3 that receives the
+    segments accepted from the parallel pass, the frames that took the serial pass, the frames.  Asynchronous on the
+    context's stream."""
+    import torch
+
+    from ._native import PngDecodeOpts
+
+    _need_context(ctx)
+    if not out.is_cuda:
+        raise UwipError(UWIP_ERR_INVALID, "device tensor expected: there is no CPU fallback")
+    n = len(streams)
+    b = batch_of(out if out.dim() != 3 else out.unsqueeze(-1))
+    bufs = [(C.c_uint8 * max(len(s), 1)).from_buffer_copy(bytes(s) or b"\0") for s in streams]
+    ptrs = (_P * max(n, 1))(*[C.cast(x, _P) for x in bufs])
+    sizes = (C.c_size_t * max(n, 1))(*[len(s) for s in streams])
+    status = torch.empty((n,), dtype=torch.int32, device=out.device)
+    opts = PngDecodeOpts(int(segmented), 0, counts.data_ptr() if counts is not None else None)
+    torch.cuda.current_stream(out.device).synchronize()
+    ctx.call("uwip_png_decode", ptrs, sizes, n, C.byref(b), C.byref(opts), _P(status.data_ptr()))
+    return status
+
+
+def decode(ctx: Context, streams: List[bytes], channels: int = 3, segmented: int = -1):
+    """``cv2.imdecode`` for a batch of equally sized PNG streams, on the device: returns ``(frames, status)``, ``frames`` a
+    uint8 device tensor ``[F, H, W, 3]`` (BGR; a grey stream replicated) or ``[F, H, W]`` (``channels=1``, grey streams only)
+    of the size of the first stream that parses (none does: ``UwipError``; no streams: an empty batch), ``status`` a list with
+    0 or ``BAD_STREAM`` / ``SIZE_MISMATCH`` per frame (the pixels of such a frame are unspecified)."""
+    import torch
+
+    _need_context(ctx)
+    if channels not in (1, 3):
+        raise UwipError(UWIP_ERR_INVALID, "channels must be 1 or 3")
+    if len(streams) == 0:
+        return torch.empty((0, 0, 0, 3) if channels == 3 else (0, 0, 0), dtype=torch.uint8, device=f"cuda:{ctx.device}"), []
+    size = None
+    for s in streams:
+        try:
+            size = info(s)[:2]
+            break
+        except UwipError:
+            continue
+    if size is None:
+        raise UwipError(UWIP_ERR_INVALID, "no stream of the batch parses: the frame size is unknown")
+    H, W = size
+    shape = (len(streams), H, W, 3) if channels == 3 else (len(streams), H, W)
+    frames = torch.empty(shape, dtype=torch.uint8, device=f"cuda:{ctx.device}")
+    status = decode_into(ctx, streams, frames, segmented)
+    ctx.sync()
+    return frames, status.cpu().tolist()
