@@ -364,6 +364,10 @@ int uwip_dehaze_histretch(uwip_ctx *ctx, const uwip_batch_u8 *in, const uwip_bat
  * L2 matcher (DESIGN.md "overlap stage"); the dense distance matrix runs on i8 MFMA. */
 typedef struct uwip_features uwip_features;
 
+/* At most this many keypoints per frame.  A frame with more candidates keeps the FIRST UWIP_MAX_KEYPOINTS, in (level, y, x)
+ * raster order, of the candidates whose response is >= the UWIP_MAX_KEYPOINTS-th largest response.  Without ties at that
+ * threshold these are the strongest; with ties the cutoff falls in raster order, and a candidate late in that order is
+ * dropped even where it is strictly stronger than the threshold (DESIGN.md "overlap stage"). */
 #define UWIP_MAX_KEYPOINTS 2048
 /* keypoint record returned by uwip_features_download (32 bytes) */
 typedef struct uwip_keypoint {

@@ -374,7 +374,7 @@ static int detect(const scale_space *S, orc_keypoint *kps /* OV_MAXKP */, int fl
                 all[cnt++] = k;
             }
     }
-    /* keep the OV_MAXKP strongest; output stays in (level, y, x) raster order */
+    /* keep the first OV_MAXKP, in (level, y, x) raster order, of the candidates >= the OV_MAXKP-th strongest response */
     size_t nout = 0;
     if (cnt <= OV_MAXKP) {
         memcpy(kps, all, cnt * sizeof(orc_keypoint));

@@ -1,6 +1,6 @@
 // videostrip overlap path, detection: resize -> gray -> non-linear scale space (Gaussian + FED diffusion) -> determinant of
-// the Hessian -> extrema -> the MAXKP strongest keypoints in raster order (DESIGN.md "overlap stage"); and calcBlur, which
-// shares the fused resize + gray kernel.
+// the Hessian -> extrema -> at most MAXKP keypoints: the first MAXKP in (level, y, x) raster order among the candidates whose
+// response is >= the MAXKP-th largest (DESIGN.md "overlap stage"); and calcBlur, which shares the fused resize + gray kernel.
 #include "overlap_internal.hpp"
 #include "device_utils.hpp"
 #include <algorithm>
