@@ -1,9 +1,10 @@
 // pngdec_check -- the device PNG decoder (uwip_png_decode_host) against the host reader the CLIs read their files with
 // (imgio::read_png, cli/imgio.hpp): the two decodes of every frame must be the same bytes.
-//   pngdec_check <file.png | list.txt> [grey] [--segmented N] [--frames B] [--time N]
+//   pngdec_check <file.png | list.txt> [grey] [--segmented N [--chunk-bytes C]] [--frames B] [--time N]
 // prints "identical <frames>", or the first difference and exits non-zero.  A frame the host reader rejects must have the
 // status UWIP_PNG_BAD_STREAM, a frame whose IHDR has another size than the first readable one UWIP_PNG_SIZE_MISMATCH.  grey: a 1-channel
-// batch.  --segmented N: uwip_png_decode_opts::segmented (default -1, the library's choice).  list.txt: one file per line.
+// batch.  --segmented N: uwip_png_decode_opts::segmented (default -1, the library's choice); --chunk-bytes C: its chunk_bytes, with
+// --segmented 2.  list.txt: one file per line.
 // --frames B: a .png file B times, as a batch of B frames.
 // --time N: the batch N times after a warm-up: the median wall milliseconds of uwip_png_decode_host (parse, upload, kernels,
 // wait), the counts of the two inflate passes, then N profiled calls: the median of the sum of the kernels' HIP-event times
@@ -18,8 +19,8 @@
 
 int main(int argc, char **argv)
 {
-    const Args a = parse_args(argc, argv, {"time", "segmented", "frames"});
-    if (a.pos.empty()) { std::printf("usage: pngdec_check <file.png | list.txt> [grey] [--segmented N] [--frames B] [--time N]\n"); return 2; }
+    const Args a = parse_args(argc, argv, {"time", "segmented", "frames", "chunk-bytes"});
+    if (a.pos.empty()) { std::printf("usage: pngdec_check <file.png | list.txt> [grey] [--segmented N [--chunk-bytes C]] [--frames B] [--time N]\n"); return 2; }
     const bool grey = a.pos.size() > 1 && a.pos[1] == "grey";
     const int channels = grey ? 1 : 3;
     const std::string &path = a.pos[0];
@@ -65,6 +66,7 @@ int main(int argc, char **argv)
         bt.step = (size_t)cols * channels; bt.frame_stride = fbytes;
         uwip_png_decode_opts opts{};
         opts.segmented = std::atoi(a.get("segmented", "-1").c_str());
+        opts.chunk_bytes = std::atoi(a.get("chunk-bytes", "0").c_str());
         opts.d_counts = (uint64_t *)d_uns;
         std::vector<int32_t> status(n, 0);
         ctx.check(uwip_png_decode_host(ctx.get(), ptr.data(), len.data(), n, &bt, &opts, status.data()));
@@ -120,7 +122,7 @@ int main(int argc, char **argv)
             ctx.check(uwip_memcpy_d2h(ctx.get(), uns, d_uns, 24));
             std::printf("frames %d  segmented %d  host_1thread_ms %.3f  host_16threads_ms %.3f  device_wall_ms_median %.3f\n", n, opts.segmented, h1, h16,
                         wall[wall.size() / 2]);
-            std::printf("segments_accepted %llu  serial_frames %llu  frames %llu\n", (unsigned long long)uns[0], (unsigned long long)uns[1],
+            std::printf("units_accepted %llu  serial_frames %llu  frames %llu\n", (unsigned long long)uns[0], (unsigned long long)uns[1],
                         (unsigned long long)uns[2]);
             // the kernels' HIP-event times: the median over N profiled calls of their sum, and the split of the median call
             ctx.check(uwip_prof_enable(ctx.get(), 1));

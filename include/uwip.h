@@ -703,15 +703,24 @@ int uwip_jpeg_decode_host(uwip_ctx *ctx, const uint8_t *const *h_streams, const 
  *   opts (NULL: the defaults): segmented 1 (and -1, the library's choice) first inflates the segments between the IDAT
  *   boundaries that follow an empty stored block (00 00 FF FF), one wavefront each, segment i at inflated offset
  *   i * uwip_png_chunk_bytes(), and accepts a frame only when every segment proves the assumption; every other
- *   frame, and with segmented 0 every frame, is inflated from its first byte by one wavefront.  The pixels and statuses do not
- *   depend on it.  d_counts, when not NULL, receives three 64-bit counts on the device: segments accepted from the parallel
- *   pass, frames that took the serial pass, frames in all.  Without a device the call fails with UWIP_ERR_HIP.
+ *   frame, and with segmented 0 every frame, is inflated from its first byte by one wavefront.  segmented 2 puts a pass between
+ *   the two for streams without such boundaries (any other encoder's): every good frame the segments did not finish and whose
+ *   zlib stream is longer than chunk_bytes is cut into chunks of chunk_bytes compressed bytes, one wavefront per chunk looks
+ *   for the first bit that parses as the start of a dynamic block and measures the blocks from there, and a frame is accepted
+ *   only when the measured chunks form one chain from the zlib header to the final block that produces exactly the frame's
+ *   bytes; the chunks are then inflated in parallel.  A frame not accepted there takes the one-wavefront pass,
+ *   which alone decides a bad status.  The pixels and statuses depend neither on segmented nor on chunk_bytes.  d_counts, when
+ *   not NULL, receives three 64-bit counts on the device: units accepted from a parallel pass (segments, and with segmented 2
+ *   the chunks of the frames accepted from found block starts), frames that took the serial pass, frames in all.  Without a
+ *   device the call fails with UWIP_ERR_HIP (UWIP_ERR_INVALID where opts itself is out of range).
  * uwip_png_decode_host: the same, waits, and returns the status array in host memory. */
 #define UWIP_PNG_BAD_STREAM    (-1)
 #define UWIP_PNG_SIZE_MISMATCH (-2)
 typedef struct uwip_png_decode_opts {
-    int32_t   segmented;   /* -1 library's choice (= 1), 0 one wavefront per stream only, 1 try IDAT-boundary segments first */
-    int32_t   reserved;    /* 0 */
+    int32_t   segmented;   /* -1 library's choice (= 1), 0 one wavefront per stream only, 1 try IDAT-boundary segments first,
+                              2 those segments, then found block starts for the frames they do not finish */
+    int32_t   chunk_bytes; /* segmented 2: compressed bytes per speculative chunk, 256 .. 1 MiB; 0 the library's choice (and
+                              0 in every other mode) */
     uint64_t *d_counts;    /* may be NULL; device, 3 x u64 */
 } uwip_png_decode_opts;
 int uwip_png_info(const uint8_t *buf, size_t len, int32_t *rows, int32_t *cols, int32_t *channels);

@@ -68,7 +68,7 @@ class JpegDecodeOpts(C.Structure):
 class PngDecodeOpts(C.Structure):
     """Mirror of ``uwip_png_decode_opts``."""
 
-    _fields_ = [("segmented", C.c_int32), ("reserved", C.c_int32), ("d_counts", C.c_void_p)]
+    _fields_ = [("segmented", C.c_int32), ("chunk_bytes", C.c_int32), ("d_counts", C.c_void_p)]
 
 
 class KeyframeConfig(C.Structure):

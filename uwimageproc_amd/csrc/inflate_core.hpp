@@ -81,4 +81,20 @@ DEFLATE_HD bool decode_slow(const CodeSet &c, const uint16_t *sorted, int lutbit
     return false;
 }
 
+// The screen of a bit position as the start of a dynamic block (png_decode.hip, found block starts), all of it necessary for
+// dynamic_header to accept the position: v holds the 17 bits BFINAL, BTYPE, HLIT, HDIST, HCLEN, w the 57 bits behind them
+// (up to 19 code lengths of 3 bits).  BTYPE 2, HLIT <= 286 - 257, HDIST <= 30 - 1, and the code-length code complete: the sum
+// of 2^(7 - l) over its non-zero lengths l is 2^7, which is what code_set_accepted asks of a kCodes set.
+DEFLATE_HD bool dynamic_start_plausible(uint32_t v, uint64_t w)
+{
+    if (((v >> 1) & 3u) != 2u || ((v >> 3) & 31u) > (uint32_t)(kMaxLL - 257) || ((v >> 8) & 31u) > (uint32_t)(kMaxDist - 1)) return false;
+    const uint32_t nc = ((v >> 13) & 15u) + 4u;
+    uint32_t sum = 0;
+    for (uint32_t i = 0; i < nc; ++i) {
+        const uint32_t l = (uint32_t)(w >> (3u * i)) & 7u;
+        sum += l ? 128u >> l : 0u;
+    }
+    return sum == 128u;
+}
+
 }  // namespace uwip_inflate

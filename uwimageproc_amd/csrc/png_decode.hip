@@ -13,6 +13,8 @@
 //                   Launch 0 decodes the segments the host parse proposed (cuts at IDAT boundaries behind 00 00 FF FF; segment
 //                   i assumed to start at inflated offset i * 32768); launch 1, one wavefront per frame, accepts a frame all of
 //                   whose segments report success and decodes every other frame again from its first byte.
+//   k_pngs_*        segmented = 2 only, between the two launches: the found block starts for streams without such cuts, with
+//                   their own header and loop bounds further down; a frame they accept is not decoded again by launch 1.
 //   k_pngd_adler    (a, b) sums of every 32 KiB piece of the inflated bytes, 128 bytes per thread;
 //   k_pngd_unfilter one wavefront per frame: the pieces' sums into the Adler-32 and its comparison with the stream's (a
 //                   mismatch is UWIP_PNG_BAD_STREAM), then the row filters undone in place, 64 rows at a time on the diagonal:
@@ -44,11 +46,20 @@ struct PFrame {                 // per frame, from the host parse
     int32_t status, spp;
     uint32_t zoff, zlen;        // its zlib stream in the uploaded bytes
     uint32_t seg0, nseg;        // its segments of launch 0 (nseg 0: none, launch 1 decodes it)
-    uint32_t pad[2];
+    uint32_t chunk0, nchunks;   // found block starts: its chunk records (nchunks + kRepairs of them); nchunks < 2: not on that path
 };
 struct PSeg { uint32_t frame, idx, off, len; };          // input bytes [off, off + len) of the frame's stream
 struct PRes { uint32_t ok, adler_pos, maxdist, pad; };   // per segment, then per frame: adler_pos in the frame's stream
 struct PGeoD { int rows, cols; uint32_t ws_stride, npieces; };
+// found block starts (segmented = 2): a chunk's measured run of whole blocks, and a frame's walk along the chain of them
+struct PChunk { uint32_t start, end, nbytes, flags, out_off, adler_pos, tries, pad; };   // bits behind the zlib header; flags: kChunk*; tries: candidates decoded
+struct PSpecFrame {
+    uint32_t open, ok;          // still walking the chain; accepted (a later kernel that finds anything amiss takes it back)
+    uint32_t end, out;          // the accepted chain ends at this bit and has produced this many bytes
+    uint32_t nacc, nrep;        // accepted chunks (their records in order: PBufs::order), repair passes used
+    uint32_t repair;            // the record the next repair pass measures from `end` into; kNone: nothing asked for
+    uint32_t adler_pos;         // of an accepted frame: where the Adler-32 lies, in bytes behind the zlib header
+};
 
 struct PBufs {
     const PFrame *fr;
@@ -60,6 +71,12 @@ struct PBufs {
     int32_t *status;
     unsigned long long *counts; // segments accepted in launch 0, frames launch 1 decoded, frames
     uint32_t nsegtot, nframes;
+    // found block starts; all null / 0 in the other modes
+    PSpecFrame *spec = nullptr;
+    PChunk *chunk = nullptr;
+    uint32_t *order = nullptr;
+    uint16_t *sym = nullptr;    // per frame ws_stride elements: a byte, or 0x8000 | k: the byte k + 1 before the chunk's first
+    uint32_t chunk_bits = 0;
 };
 
 __device__ __forceinline__ uint32_t frame_total(const PGeoD &g, int spp) { return (uint32_t)g.rows * (1u + (uint32_t)g.cols * (uint32_t)spp); }
@@ -200,6 +217,14 @@ __global__ __launch_bounds__(64) void k_pngd_inflate(PBufs B, PGeoD g, int pass)
         if (f == 0u && lane == 0u) B.counts[2] = B.nframes;
         if (fr.status != 0) {
             if (lane == 0) { B.status[f] = fr.status; B.res[rslot] = PRes{0u, 0u, 0u, 0u}; }
+            return;
+        }
+        if (B.spec && B.spec[f].ok) {                         // accepted from found block starts: its bytes are in the workspace
+            if (lane == 0) {
+                B.status[f] = 0;
+                B.res[rslot] = PRes{1u, 2u + B.spec[f].adler_pos, 0u, 0u};
+                atomicAdd(&B.counts[0], (unsigned long long)B.spec[f].nacc);
+            }
             return;
         }
         if (fr.nseg) {
@@ -434,7 +459,7 @@ void plan_frame(PFrame &d, const uwip_pngd::Parsed &p, int rows, int cols, int s
     d.zoff = (uint32_t)pl.src_bytes; d.zlen = (uint32_t)p.zlen;
     pl.src_bytes += (p.zlen + 31) & ~(size_t)15;
     d.seg0 = (uint32_t)segs.size(); d.nseg = 0;
-    if (segmented) {
+    if (segmented == 1 || (segmented == 2 && !p.cuts.empty())) {      // 2: a stream without cuts is left to the found block starts
         size_t at = 2;
         uint32_t i = 0;
         for (size_t c : p.cuts) { segs.push_back(PSeg{(uint32_t)f, i++, (uint32_t)at, (uint32_t)(c - at)}); at = c; }
@@ -442,6 +467,330 @@ void plan_frame(PFrame &d, const uwip_pngd::Parsed &p, int rows, int cols, int s
         d.nseg = i;
     }
     if (pl.src_bytes >= ((size_t)1 << 31)) pl.too_large = true;
+}
+
+}  // namespace
+
+// ---- found block starts (segmented = 2) ------------------------------------------------------------------------
+// A stream without flush points is cut into chunks of chunk_bytes compressed bytes.  Kernels, each one launch, no workgroup
+// waits for another -- the order between chunks comes from the kernel boundaries alone:
+//   k_pngs_begin    one thread per frame: which frames take this path (good, at least two chunks, not accepted from segments);
+//   k_pngs_measure  one wavefront per (chunk, frame).  Chunk 0 starts behind the zlib header.  Every other chunk looks for
+//                   the first bit of its range that passes as the start of a dynamic block: the lanes screen kScreen x 64
+//                   positions a round in registers (dynamic_start_plausible), the first that passes gets dynamic_header, and
+//                   from there the wavefront decodes lengths only -- no store, no window -- through whole blocks up to the
+//                   first block boundary at or behind the end of its range.  A decode that fails discards the candidate and
+//                   the search goes on one bit later.  The record: start bit, end bit, bytes produced.
+//                   As a repair pass (one wavefront per frame) it measures from the accepted chain's end, any block type;
+//   k_pngs_verify   one thread per frame walks the chain: the chunk whose range holds the chain's end is accepted iff it
+//                   starts exactly there, and gets the chain's byte count as its output offset; otherwise a repair pass is
+//                   asked for (kRepairs of them per call), and the frame is given up when they are spent;
+//   k_pngs_write    one wavefront per accepted chunk decodes again, as k_pngd_inflate does, into 16-bit elements;
+//   k_pngs_window   one workgroup per frame, the chunks in order: the markers in a chunk's last 32 768 elements become bytes;
+//   k_pngs_resolve  one workgroup per accepted chunk: elements to bytes in the frame's workspace.
+// What bounds the loops on untrusted bytes: the search position only grows and ends at the chunk's range, and at most
+// kMaxTries candidates of a chunk get the full decode; a decode step consumes at least one bit or ends the run, and no bit
+// position passes the stream's length by more than one token (peek32 reads zeros there without a load); a measured run may
+// not produce more than the frame's bytes; verify accepts a chunk only inside the frame (out_off + nbytes <= total, total <=
+// ws_stride), each acceptance moves to a later range, so its loop takes at most nchunks steps; every store of k_pngs_write is
+// checked against the chunk's measured length before its token is taken; k_pngs_window and k_pngs_resolve form a source index
+// only where k + 1 <= out_off, and their element loops run over measured lengths; table indices as in k_pngd_inflate.
+namespace {
+
+constexpr uint32_t kNone = 0xFFFFFFFFu;
+constexpr uint32_t kChunkValid = 1u, kChunkFinal = 2u;
+constexpr uint32_t kMarker = 0x8000u;
+constexpr int kRepairs = 4;                              // repair passes per call
+constexpr int kScreen = 4;                               // bit positions a lane screens per round
+constexpr int kMaxTries = 256;                           // candidates of one chunk that get the full decode
+constexpr uint32_t kSpecChunkDefault = 16384;            // chunk_bytes 0
+
+struct SpecRun { uint32_t end, nbytes, adler_pos; bool ok, final_blk; };
+
+// Whole blocks from the block header at bit `pos` up to the first block boundary at or behind bit `stop`, or through the final
+// block.  out == nullptr: lengths only, at most `win` bytes.  Otherwise the 16-bit elements of out[0, win): a byte, or kMarker | k
+// for "the byte k + 1 before out[0]" -- a match copies elements, so a reference into the bytes before the chunk is handed on --
+// and a distance that reaches before the stream's first byte (abs0 bytes lie before out[0]) fails the run.
+__device__ SpecRun spec_run(Tables &T, const uint8_t *src, uint32_t a0, uint32_t len, uint32_t pos, uint32_t stop, bool first_dynamic,
+                            uint16_t *out, uint32_t win, uint32_t abs0)
+{
+    const uint32_t lane = threadIdx.x, lenbits = len * 8u;
+    SpecRun r{0u, 0u, 0u, false, false};
+    uint32_t o = 0;
+    for (bool first = true;; first = false) {
+        uint32_t v = peek32(src, a0, len, pos);
+        const bool final_blk = v & 1u;
+        const uint32_t type = (v >> 1) & 3u;
+        pos += 3u;
+        if (pos > lenbits || type == 3u || (first && first_dynamic && type != 2u)) return r;
+        if (type == 0u) {
+            pos = (pos + 7u) & ~7u;
+            if (pos + 32u > lenbits) return r;
+            v = peek32(src, a0, len, pos);
+            const uint32_t L = v & 0xFFFFu;
+            pos += 32u;
+            const uint32_t by = pos >> 3;
+            if ((L ^ 0xFFFFu) != (v >> 16) || L > len - by || L > win - o) return r;
+            if (out) {
+                for (uint32_t j = lane; j < L; j += 64u) out[o + j] = src[a0 + by + j];
+                __syncthreads();
+            }
+            o += L; pos += L * 8u;
+        } else {
+            if (type == 1u) {
+                for (uint32_t i = lane; i < (uint32_t)(kFixedLL + kFixedDist); i += 64u) T.lens[i] = (uint8_t)fixed_len((int)i);
+                __syncthreads();
+                build_table(T.lens, kFixedLL, kLens, kLLBits, T.ll, T.ll_sorted, T.ll_set);
+                build_table(T.lens + kFixedLL, kFixedDist, kDists, kDBits, T.d, T.d_sorted, T.d_set);
+            } else if (!dynamic_header(T, src, a0, len, pos)) return r;
+            for (bool eob = false; !eob;) {
+                // a round as in k_pngd_inflate: up to 64 tokens when they are stored, the whole block when they are not
+                uint32_t ntok = 0, o_r = o;
+                while (!out || ntok < (uint32_t)kRound) {
+                    uint32_t l, sym;
+                    v = peek32(src, a0, len, pos);
+                    if (!decode_sym(T.ll, kLLBits, T.ll_set, T.ll_sorted, v, l, sym)) return r;
+                    pos += l;
+                    if (sym < 256u) {
+                        if (o_r >= win) return r;
+                        if (out && lane == ntok) { T.tlen[lane] = 1; T.tval[lane] = (uint16_t)sym; T.tout[lane] = o_r; }
+                        ++ntok; ++o_r;
+                    } else if (sym == 256u) { eob = true; break; }
+                    else {
+                        if (sym >= (uint32_t)kMaxLL) return r;
+                        const uint32_t idx = sym - 257u, eb = length_extra(idx);
+                        const uint32_t mlen = length_base(idx) + ((v >> l) & ((1u << eb) - 1u));
+                        pos += eb;
+                        v = peek32(src, a0, len, pos);
+                        uint32_t l2, dsym;
+                        if (!decode_sym(T.d, kDBits, T.d_set, T.d_sorted, v, l2, dsym) || dsym >= (uint32_t)kMaxDist) return r;
+                        const uint32_t de = dist_extra(dsym), dist = dist_base(dsym) + ((v >> l2) & ((1u << de) - 1u));   // <= 32768
+                        pos += l2 + de;
+                        if (mlen > win - o_r || (out && dist > abs0 + o_r)) return r;
+                        if (out && lane == ntok) { T.tlen[lane] = (uint16_t)mlen; T.tval[lane] = (uint16_t)(dist - 1u); T.tout[lane] = o_r; }
+                        ++ntok; o_r += mlen;
+                    }
+                    if (pos > lenbits) return r;
+                }
+                if (pos > lenbits) return r;
+                if (out) {
+                    __syncthreads();
+                    if (lane < ntok && T.tlen[lane] == 1) out[T.tout[lane]] = T.tval[lane];
+                    __syncthreads();
+                    uint32_t dirty = kNone;
+                    for (uint32_t i = 0; i < ntok; ++i) {
+                        const uint32_t ml = T.tlen[i];
+                        if (ml == 1u) continue;
+                        const uint32_t dist = (uint32_t)T.tval[i] + 1u, to = T.tout[i];
+                        const int s0 = (int)to - (int)dist;                              // before out[0]: markers, nothing is read
+                        if (dirty != kNone && s0 + (int)min(ml, dist) > (int)dirty) { __syncthreads(); dirty = kNone; }
+                        for (uint32_t j = lane; j < ml; j += 64u) {
+                            const int q = s0 + (int)(dist >= ml ? j : j % dist);         // < to; -q - 1 <= dist - 1 <= 32767
+                            out[to + j] = q >= 0 ? out[q] : (uint16_t)(kMarker | (uint32_t)(-q - 1));
+                        }
+                        dirty = min(dirty, to);
+                    }
+                    __syncthreads();
+                }
+                o = o_r;
+            }
+        }
+        if (final_blk) {
+            pos = (pos + 7u) & ~7u;
+            r.adler_pos = pos >> 3;
+            if (r.adler_pos + 4u > len) return r;                                        // the Adler-32 follows the last block
+            r.final_blk = true;
+            break;
+        }
+        if (pos >= stop) break;
+    }
+    r.ok = true; r.end = pos; r.nbytes = o;
+    return r;
+}
+
+__global__ __launch_bounds__(64) void k_pngs_begin(PBufs B)
+{
+    const uint32_t f = blockIdx.x * 64u + threadIdx.x;
+    if (f >= B.nframes) return;
+    const PFrame fr = B.fr[f];
+    bool open = fr.status == 0 && fr.nchunks >= 2u;
+    if (open && fr.nseg) {                                   // its segments ran: accepted there, it is finished
+        uint32_t bad = 0;
+        for (uint32_t s = 0; s < fr.nseg; ++s) bad += B.res[fr.seg0 + s].ok ? 0u : 1u;
+        open = bad != 0u;
+    }
+    B.spec[f] = PSpecFrame{open ? 1u : 0u, 0u, 0u, 0u, 0u, 0u, kNone, 0u};
+}
+
+// repair 0: block (c, f) is chunk c of frame f.  repair 1: block (0, f) measures from the chain's end, where verify asked for it.
+__global__ __launch_bounds__(64) void k_pngs_measure(PBufs B, PGeoD g, int repair)
+{
+    __shared__ Tables T;
+    __shared__ uint32_t s_first[2];
+    const uint32_t lane = threadIdx.x, f = blockIdx.y;
+    const PFrame fr = B.fr[f];
+    const PSpecFrame sp = B.spec[f];
+    if (!sp.open) return;
+    uint32_t c = blockIdx.x, lo, slot;
+    if (repair) {
+        if (sp.repair == kNone) return;
+        lo = sp.end; c = lo / B.chunk_bits; slot = sp.repair;
+    } else {
+        if (c >= fr.nchunks) return;
+        lo = c * B.chunk_bits; slot = c;
+    }
+    const uint32_t a0 = fr.zoff + 2u, len = fr.zlen - 2u, lenbits = len * 8u, total = frame_total(g, fr.spp);
+    const uint32_t hi = min((c + 1u) * B.chunk_bits, lenbits);
+    const uint8_t *src = B.src;
+    SpecRun r{0u, 0u, 0u, false, false};
+    uint32_t start = lo;
+    int tries = 0;
+    if (repair || c == 0u) r = spec_run(T, src, a0, len, lo, hi, false, nullptr, total, 0u);
+    else {
+        uint32_t p = lo;
+        int par = 0;
+        while (p < hi && tries < kMaxTries) {
+            if (lane == 0) s_first[par] = kNone;
+            __syncthreads();
+            uint32_t mine = kNone;
+            for (int j = 0; j < kScreen && mine == kNone; ++j) {
+                const uint32_t q = p + lane + 64u * (uint32_t)j;
+                if (q >= hi) break;
+                const uint32_t v = peek32(src, a0, len, q);
+                const uint64_t w = (uint64_t)peek32(src, a0, len, q + 17u) | ((uint64_t)peek32(src, a0, len, q + 49u) << 32);
+                if (dynamic_start_plausible(v, w)) mine = q;
+            }
+            if (mine != kNone) atomicMin(&s_first[par], mine);
+            __syncthreads();
+            const uint32_t q = s_first[par];
+            par ^= 1;
+            if (q == kNone) { p += 64u * (uint32_t)kScreen; continue; }
+            ++tries;
+            r = spec_run(T, src, a0, len, q, hi, true, nullptr, total, 0u);
+            if (r.ok) { start = q; break; }
+            p = q + 1u;
+        }
+    }
+    if (lane == 0)
+        B.chunk[fr.chunk0 + slot] = PChunk{start, r.end, r.nbytes, r.ok ? (kChunkValid | (r.final_blk ? kChunkFinal : 0u)) : 0u, 0u, r.adler_pos, (uint32_t)tries, 0u};
+}
+
+__global__ __launch_bounds__(64) void k_pngs_verify(PBufs B, PGeoD g)
+{
+    const uint32_t f = blockIdx.x * 64u + threadIdx.x;
+    if (f >= B.nframes) return;
+    PSpecFrame sp = B.spec[f];
+    if (!sp.open) return;
+    const PFrame fr = B.fr[f];
+    const uint32_t total = frame_total(g, fr.spp);
+    PChunk *ch = B.chunk + fr.chunk0;
+    uint32_t *order = B.order + fr.chunk0;
+    sp.open = 0u;                                            // unless a repair is asked for below
+    for (;;) {                                               // an accepted chunk ends in a later range (or the stream): <= nchunks steps
+        const bool repaired = sp.repair != kNone;
+        uint32_t slot = sp.repair;
+        sp.repair = kNone;
+        if (!repaired) {
+            slot = sp.end / B.chunk_bits;
+            if (slot >= fr.nchunks) break;
+        }
+        const PChunk k = ch[slot];
+        if (!(k.flags & kChunkValid) || k.start != sp.end) {  // nothing starts where the chain ends
+            if (!repaired && sp.nrep < (uint32_t)kRepairs) { sp.repair = fr.nchunks + sp.nrep; ++sp.nrep; sp.open = 1u; }
+            break;
+        }
+        if (k.nbytes > total - sp.out || sp.nacc >= fr.nchunks + (uint32_t)kRepairs) break;
+        ch[slot].out_off = sp.out;
+        order[sp.nacc++] = slot;
+        sp.end = k.end; sp.out += k.nbytes;
+        if (k.flags & kChunkFinal) {
+            sp.ok = sp.out == total ? 1u : 0u;
+            sp.adler_pos = k.adler_pos;
+            break;
+        }
+    }
+    B.spec[f] = sp;
+}
+
+__global__ __launch_bounds__(64) void k_pngs_write(PBufs B, PGeoD g)
+{
+    __shared__ Tables T;
+    const uint32_t f = blockIdx.y;
+    const PSpecFrame sp = B.spec[f];
+    if (!sp.ok || blockIdx.x >= sp.nacc) return;
+    const PFrame fr = B.fr[f];
+    const PChunk k = B.chunk[fr.chunk0 + B.order[fr.chunk0 + blockIdx.x]];
+    uint16_t *out = B.sym + (size_t)f * g.ws_stride + k.out_off;
+    const SpecRun r = spec_run(T, B.src, fr.zoff + 2u, fr.zlen - 2u, k.start, k.end, false, out, k.nbytes, k.out_off);
+    if (!(r.ok && r.end == k.end && r.nbytes == k.nbytes) && threadIdx.x == 0) B.spec[f].ok = 0u;
+}
+
+__global__ __launch_bounds__(256) void k_pngs_window(PBufs B, PGeoD g)
+{
+    const uint32_t f = blockIdx.x, t = threadIdx.x;
+    const PSpecFrame sp = B.spec[f];
+    if (!sp.ok) return;
+    const PFrame fr = B.fr[f];
+    uint16_t *sym = B.sym + (size_t)f * g.ws_stride;
+    bool bad = false;
+    for (uint32_t i = 0; i < sp.nacc; ++i) {
+        const PChunk k = B.chunk[fr.chunk0 + B.order[fr.chunk0 + i]];
+        // a marker's source lies in the 32 768 bytes before this chunk: in the last 32 768 elements of earlier chunks, all bytes by now
+        for (uint32_t e = (k.nbytes > (uint32_t)kChunk ? k.nbytes - (uint32_t)kChunk : 0u) + t; e < k.nbytes; e += 256u) {
+            const uint32_t v = sym[k.out_off + e];
+            if (!(v & kMarker)) continue;
+            const uint32_t back = (v & 0x7FFFu) + 1u;
+            const uint32_t s = back <= k.out_off ? sym[k.out_off - back] : (uint32_t)kMarker;
+            if (s & kMarker) bad = true;
+            else sym[k.out_off + e] = (uint16_t)s;
+        }
+        __syncthreads();
+    }
+    if (bad) B.spec[f].ok = 0u;
+}
+
+__global__ __launch_bounds__(256) void k_pngs_resolve(PBufs B, PGeoD g)
+{
+    const uint32_t f = blockIdx.y, t = threadIdx.x;
+    const PSpecFrame sp = B.spec[f];
+    if (!sp.ok || blockIdx.x >= sp.nacc) return;
+    const PFrame fr = B.fr[f];
+    const PChunk k = B.chunk[fr.chunk0 + B.order[fr.chunk0 + blockIdx.x]];
+    const uint16_t *sym = B.sym + (size_t)f * g.ws_stride;
+    uint8_t *out = B.ws + (size_t)f * g.ws_stride + k.out_off;
+    bool bad = false;
+    for (uint32_t e = t; e < k.nbytes; e += 256u) {
+        uint32_t v = sym[k.out_off + e];
+        if (v & kMarker) {
+            const uint32_t back = (v & 0x7FFFu) + 1u;
+            v = back <= k.out_off ? sym[k.out_off - back] : (uint32_t)kMarker;
+            if (v & kMarker) bad = true;
+        }
+        out[e] = (uint8_t)v;
+    }
+    if (bad) B.spec[f].ok = 0u;
+}
+
+// ---- the host side of the found block starts ----
+// chunk_bytes 0 is the library's choice; the records of frame f: nchunks for its chunks, kRepairs behind them
+uint32_t spec_chunk_bytes(int32_t asked) { return asked ? (uint32_t)asked : kSpecChunkDefault; }
+void spec_plan_frame(PFrame &d, uint32_t chunk_bytes, size_t &nslots, uint32_t &maxslots)
+{
+    const size_t len = d.zlen - 2u;
+    d.nchunks = (uint32_t)((len + chunk_bytes - 1) / chunk_bytes);
+    d.chunk0 = (uint32_t)nslots;
+    if (d.nchunks < 2u) { d.nchunks = 0u; return; }
+    nslots += d.nchunks + kRepairs;
+    maxslots = std::max(maxslots, d.nchunks + (uint32_t)kRepairs);
+}
+size_t spec_meta_bytes(size_t n, size_t nslots) { return n * sizeof(PSpecFrame) + nslots * (sizeof(PChunk) + 4) + 16; }
+void spec_bind(PBufs &B, void *meta, void *sym, size_t n, size_t nslots, uint32_t chunk_bytes)
+{
+    B.spec = static_cast<PSpecFrame *>(meta);
+    B.chunk = reinterpret_cast<PChunk *>(B.spec + n);
+    B.order = reinterpret_cast<uint32_t *>(B.chunk + nslots);
+    B.sym = static_cast<uint16_t *>(sym);
+    B.chunk_bits = chunk_bytes * 8u;
 }
 
 }  // namespace
@@ -458,7 +807,10 @@ UWIP_API int uwip_png_info(const uint8_t *buf, size_t len, int32_t *rows, int32_
 UWIP_API int uwip_png_decode(uwip_ctx *ctx, const uint8_t *const *h_streams, const size_t *h_sizes, int n, const uwip_batch_u8 *out,
                              const uwip_png_decode_opts *opts, int32_t *d_status)
 {
+    const int mode = opts ? opts->segmented : -1, asked = opts ? opts->chunk_bytes : 0;
+    const bool opts_ok = mode >= -1 && mode <= 2 && (asked == 0 || (mode == 2 && asked >= 256 && asked <= (1 << 20)));
     if (!ctx) {                                               // no context: because there is no device, or a plain bad argument
+        if (!opts_ok) return UWIP_ERR_INVALID;
         int ndev = 0;
         return (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) ? UWIP_ERR_HIP : UWIP_ERR_INVALID;
     }
@@ -466,14 +818,15 @@ UWIP_API int uwip_png_decode(uwip_ctx *ctx, const uint8_t *const *h_streams, con
     if (rc) return rc;
     UWIP_REQUIRE(ctx, n >= 0 && n <= 65535, "at most 65535 frames per call");
     UWIP_REQUIRE(ctx, out->frames == n, "the batch must hold one frame per stream");
-    UWIP_REQUIRE(ctx, !opts || (opts->segmented >= -1 && opts->segmented <= 1 && opts->reserved == 0), "segmented must be -1, 0 or 1");
+    UWIP_REQUIRE(ctx, opts_ok, "segmented must be -1, 0, 1 or 2; chunk_bytes 0, or 256 .. 1 MiB with segmented 2");
     if (n == 0) return UWIP_OK;
     UWIP_REQUIRE(ctx, h_streams != nullptr && h_sizes != nullptr && d_status != nullptr, "null argument");
     UWIP_REQUIRE(ctx, out->rows >= 1 && out->cols >= 1, "empty frame");
     UWIP_REQUIRE(ctx, out->rows <= 65535 && out->cols <= 65535, "at most 65535 rows / columns");
     for (int f = 0; f < n; ++f) UWIP_REQUIRE(ctx, h_streams[f] != nullptr || h_sizes[f] == 0, "null stream");
     for (int f = 0; f < n; ++f) UWIP_REQUIRE(ctx, h_sizes[f] < ((size_t)1 << 28), "a stream of 256 MiB or more");
-    const int segmented = (opts && opts->segmented == 0) ? 0 : 1;
+    const int segmented = mode < 0 ? 1 : mode;
+    const uint32_t chunk_bytes = spec_chunk_bytes(asked);
     const size_t wsb = ws_bytes(out->rows, out->cols);
     UWIP_REQUIRE(ctx, wsb < ((size_t)1 << 31), "frame too large");
 
@@ -481,6 +834,8 @@ UWIP_API int uwip_png_decode(uwip_ctx *ctx, const uint8_t *const *h_streams, con
     std::vector<PFrame> fr((size_t)n);
     std::vector<PSeg> segs;
     PPlan pl;
+    size_t nslots = 0;                                        // chunk records of the found block starts
+    uint32_t maxslots = 0;
     for (int f = 0; f < n; ++f) {
         PFrame &d = fr[f];
         std::memset(&d, 0, sizeof d);
@@ -489,9 +844,12 @@ UWIP_API int uwip_png_decode(uwip_ctx *ctx, const uint8_t *const *h_streams, con
         if (d.status == 0 && ((int64_t)p.H != out->rows || (int64_t)p.W != out->cols || (p.spp >= 3 && out->channels == 1)))
             d.status = UWIP_PNG_SIZE_MISMATCH;
         d.spp = d.status == 0 ? p.spp : 1;
-        if (d.status == 0) plan_frame(d, p, out->rows, out->cols, segmented, segs, f, pl);
+        if (d.status == 0) {
+            plan_frame(d, p, out->rows, out->cols, segmented, segs, f, pl);
+            if (segmented == 2) spec_plan_frame(d, chunk_bytes, nslots, maxslots);
+        }
     }
-    UWIP_REQUIRE(ctx, !pl.too_large && segs.size() < ((size_t)1 << 24), "batch too large for one call");
+    UWIP_REQUIRE(ctx, !pl.too_large && segs.size() < ((size_t)1 << 24) && nslots < ((size_t)1 << 24), "batch too large for one call");
 
     // The page-locked staging buffer holds the descriptors, the segments, then the zlib streams.  It is free again once the
     // previous call's upload has finished: poll that event (the stream is not drained) before the buffer is touched.
@@ -514,6 +872,12 @@ UWIP_API int uwip_png_decode(uwip_ctx *ctx, const uint8_t *const *h_streams, con
     // the small arrays share one buffer: the counts, the results, the Adler sums
     uint64_t *meta = static_cast<uint64_t *>(uwip_ws(ctx, "pngdec.meta", 32 + (nsegtot + n) * sizeof(PRes) + (size_t)n * npieces * 8));
     if (!d_in || !ws || !meta) return UWIP_ERR_NOMEM;
+    void *spec_meta = nullptr, *spec_sym = nullptr;          // only where the found block starts are used
+    if (nslots) {
+        spec_meta = uwip_ws(ctx, "pngdec.chunks", spec_meta_bytes((size_t)n, nslots));
+        spec_sym = uwip_ws(ctx, "pngdec.symbols", ((size_t)n * wsb + 16) * 2);
+        if (!spec_meta || !spec_sym) return UWIP_ERR_NOMEM;
+    }
     UWIP_HIP(ctx, hipMemcpyAsync(d_in, h_in, in_bytes, hipMemcpyHostToDevice, ctx->stream));
     UWIP_HIP(ctx, hipEventRecord(ctx->pngd_ev, ctx->stream));
 
@@ -533,6 +897,20 @@ UWIP_API int uwip_png_decode(uwip_ctx *ctx, const uint8_t *const *h_streams, con
     if (nsegtot) {
         uwip_kscope ks(ctx, "k_pngd_inflate_segments");
         k_pngd_inflate<<<(unsigned)nsegtot, 64, 0, ctx->stream>>>(B, g, 0);
+    }
+    if (nslots) {
+        spec_bind(B, spec_meta, spec_sym, (size_t)n, nslots, chunk_bytes);
+        const unsigned nb = uwip_cdiv((size_t)n, 64);
+        { uwip_kscope ks(ctx, "k_pngs_begin"); k_pngs_begin<<<nb, 64, 0, ctx->stream>>>(B); }
+        { uwip_kscope ks(ctx, "k_pngs_measure"); k_pngs_measure<<<dim3(maxslots - kRepairs, n), 64, 0, ctx->stream>>>(B, g, 0); }
+        { uwip_kscope ks(ctx, "k_pngs_verify"); k_pngs_verify<<<nb, 64, 0, ctx->stream>>>(B, g); }
+        for (int r = 0; r < kRepairs; ++r) {
+            { uwip_kscope ks(ctx, "k_pngs_measure_repair"); k_pngs_measure<<<dim3(1, n), 64, 0, ctx->stream>>>(B, g, 1); }
+            { uwip_kscope ks(ctx, "k_pngs_verify"); k_pngs_verify<<<nb, 64, 0, ctx->stream>>>(B, g); }
+        }
+        { uwip_kscope ks(ctx, "k_pngs_write"); k_pngs_write<<<dim3(maxslots, n), 64, 0, ctx->stream>>>(B, g); }
+        { uwip_kscope ks(ctx, "k_pngs_window"); k_pngs_window<<<n, 256, 0, ctx->stream>>>(B, g); }
+        { uwip_kscope ks(ctx, "k_pngs_resolve"); k_pngs_resolve<<<dim3(maxslots, n), 256, 0, ctx->stream>>>(B, g); }
     }
     {
         uwip_kscope ks(ctx, "k_pngd_inflate");

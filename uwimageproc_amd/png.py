@@ -84,11 +84,12 @@ def info(stream: bytes) -> Tuple[int, int, int]:
     return r.value, c.value, ch.value
 
 
-def decode_into(ctx: Context, streams: List[bytes], out, segmented: int = -1, counts=None):
+def decode_into(ctx: Context, streams: List[bytes], out, segmented: int = -1, counts=None, chunk_bytes: int = 0):
     """Decodes ``streams`` into the device tensor ``out`` (``[F, H, W, 3]`` BGR or ``[F, H, W]`` grey, any strides with packed
     pixels); returns the int32 device tensor of per-frame statuses.  ``counts``: an int64 device tensor of 3 that receives the
-    segments accepted from the parallel pass, the frames that took the serial pass, the frames.  Asynchronous on the
-    context's stream."""
+    units accepted from a parallel pass (segments; with ``segmented=2`` also the chunks of found block starts), the frames that
+    took the serial pass, the frames.  ``chunk_bytes``: with ``segmented=2`` the compressed bytes per speculative chunk (256 ..
+    1 MiB; 0 the library's choice); the result does not depend on it.  Asynchronous on the context's stream."""
     import torch
 
     from ._native import PngDecodeOpts
@@ -102,17 +103,18 @@ def decode_into(ctx: Context, streams: List[bytes], out, segmented: int = -1, co
     ptrs = (_P * max(n, 1))(*[C.cast(x, _P) for x in bufs])
     sizes = (C.c_size_t * max(n, 1))(*[len(s) for s in streams])
     status = torch.empty((n,), dtype=torch.int32, device=out.device)
-    opts = PngDecodeOpts(int(segmented), 0, counts.data_ptr() if counts is not None else None)
+    opts = PngDecodeOpts(int(segmented), int(chunk_bytes), counts.data_ptr() if counts is not None else None)
     torch.cuda.current_stream(out.device).synchronize()
     ctx.call("uwip_png_decode", ptrs, sizes, n, C.byref(b), C.byref(opts), _P(status.data_ptr()))
     return status
 
 
-def decode(ctx: Context, streams: List[bytes], channels: int = 3, segmented: int = -1):
+def decode(ctx: Context, streams: List[bytes], channels: int = 3, segmented: int = -1, chunk_bytes: int = 0):
     """``cv2.imdecode`` for a batch of equally sized PNG streams, on the device: returns ``(frames, status)``, ``frames`` a
     uint8 device tensor ``[F, H, W, 3]`` (BGR; a grey stream replicated) or ``[F, H, W]`` (``channels=1``, grey streams only)
     of the size of the first stream that parses (none does: ``UwipError``; no streams: an empty batch), ``status`` a list with
-    0 or ``BAD_STREAM`` / ``SIZE_MISMATCH`` per frame (the pixels of such a frame are unspecified)."""
+    0 or ``BAD_STREAM`` / ``SIZE_MISMATCH`` per frame (the pixels of such a frame are unspecified).  ``segmented=2`` inflates
+    streams of other encoders in parallel from found block starts (``chunk_bytes`` as in ``decode_into``)."""
     import torch
 
     _need_context(ctx)
@@ -132,6 +134,6 @@ def decode(ctx: Context, streams: List[bytes], channels: int = 3, segmented: int
     H, W = size
     shape = (len(streams), H, W, 3) if channels == 3 else (len(streams), H, W)
     frames = torch.empty(shape, dtype=torch.uint8, device=f"cuda:{ctx.device}")
-    status = decode_into(ctx, streams, frames, segmented)
+    status = decode_into(ctx, streams, frames, segmented, chunk_bytes=chunk_bytes)
     ctx.sync()
     return frames, status.cpu().tolist()
