@@ -5,7 +5,7 @@
 // on the frames of a Motion-JPEG .avi or of a frame list, in batches through page-locked host buffers
 // (uwip_pipe_step_host: batch k + 1 is uploaded and batch k - 1 leaves while batch k's kernels run).
 //   uwpipe [-b N] [-c LETTERS] [-w N] [--guard-s] [--min6] [--relative-threshold] [--png] [--device-jpeg] [--device-png] [--device-decode]
-//          [--keyframes [-k N] [-p X] [--lookback D]] <video.avi | frame_list.txt> <output_prefix>
+//          [--streams] [--keyframes [-k N] [-p X] [--lookback D]] <video.avi | frame_list.txt> <output_prefix>
 // writes <prefix>NNNN.jpg (the enhanced frames) and <prefix>uwpipe_report.txt (TSV: ID, Filename, Overlap, BS, CL).
 // --keyframes: the overlap stage runs videostrip's key-frame selector (main.cpp:284-394) on the enhanced frames, on the
 // device (uwip_pipe_keyframe_chain); <prefix>videostrip_report.txt gets its rows with the reference's columns (ID, Frame,
@@ -20,6 +20,12 @@
 // (--device-jpeg) or by a plain download; a frame with a negative status is decoded on the host and copied into its slot.
 // The files and both reports are the same bytes as without the flag.  The steps run one after another here (decode, step,
 // wait, results): the overlap of upload, kernels and download that uwip_pipe_step_host gives the raw-frame path is not used.
+// --streams (implies --device-decode and device output: .png with --png / --device-png, else .jpg): the compressed frames of a step
+// go to uwip_pipe_step_streams, which returns when the step is queued; the loop queues step k, then collects step k - 1
+// (uwip_pipe_collect) and writes its files while the device works on step k.  Only compressed bytes cross the link.  With
+// --keyframes only the key frames are encoded and written -- what the reference's videostrip writes (main.cpp:368-381) --, named as
+// videostrip_report.txt names them.  The files written and both reports are the same bytes as without the flag.  There is no host
+// fallback here: a frame the device decoder leaves, or a stream that outgrows the raw frame size, ends the run with a message.
 // Defaults are the reference's rules (uwip_pipe_config_default); the three switches are the library's opt-in deviations.
 #include <algorithm>
 #include <cstring>
@@ -33,7 +39,7 @@ int main(int argc, char **argv)
     if (a.pos.size() < 2 || a.has("h") || a.has("help")) {
         std::printf("uwpipe - bgdehaze -> histretch -> aclahe -> overlap of every frame against its predecessor\n"
                     "usage: uwpipe [-b N] [-c LETTERS] [-w N] [--guard-s] [--min6] [--relative-threshold] [--png] [--device-jpeg]\n"
-                    "              [--device-png] [--device-decode] [--keyframes [-k N] [-p X] [--lookback D]] <video.avi (Motion-JPEG) | frame_list.txt> <output_prefix>\n"
+                    "              [--device-png] [--device-decode] [--streams] [--keyframes [-k N] [-p X] [--lookback D]] <video.avi (Motion-JPEG) | frame_list.txt> <output_prefix>\n"
                     "  -b N      frames per step (default 8)\n"
                     "  -c L      histretch letters (default RGB)\n"
                     "  -w N      bgdehaze window (default 15)\n"
@@ -41,6 +47,7 @@ int main(int argc, char **argv)
                     "  --device-jpeg   encode the .jpg files on the device (same bytes; ignored with --png)\n"
                     "  --device-png    write .png files encoded on the device (the pixels of --png; the bytes differ)\n"
                     "  --device-decode decode the input JPEG and PNG frames on the device (same files; a frame the device decoder leaves is decoded on the host)\n"
+                    "  --streams       compressed frames in, compressed frames out, queued without a host wait (with --keyframes only the key frames are written)\n"
                     "  --keyframes   select key frames as videostrip does (report: <prefix>videostrip_report.txt)\n"
                     "  -k N          frames of the refinement window (default 11)\n"
                     "  -p X          minOverlap (default 0.4)\n"
@@ -102,7 +109,8 @@ int main(int argc, char **argv)
             kreport << "***************************************\nID\tFrame\tFilename\tOverlap\tBlur\n";
         }
         // --device-decode: the compressed frames of a step, the device batches it runs on; no raw frames are uploaded
-        const bool device_decode = a.has("device-decode");
+        const bool streams = a.has("streams");
+        const bool device_decode = a.has("device-decode") || streams;
         for (int s = 0; s < 2 && !device_decode; ++s) CK(uwip_host_alloc(ctx, fbytes * B, &h_in[s]), "uwip_host_alloc");
         CK(uwip_host_alloc(ctx, fbytes * B, &h_out), "uwip_host_alloc");
         CK(uwip_host_alloc(ctx, sizeof(float) * B, &h_ratio), "uwip_host_alloc");
@@ -136,7 +144,7 @@ int main(int argc, char **argv)
         std::vector<size_t> jlen(B);
         std::vector<int32_t> jstatus(B);
         uwip_batch_u8 bin{}, bout{};
-        if (device_decode) {
+        if (device_decode && !streams) {
             CK(uwip_malloc(ctx, fbytes * B, &d_in), "uwip_malloc");
             CK(uwip_malloc(ctx, fbytes * B, &d_out), "uwip_malloc");
             CK(uwip_malloc(ctx, sizeof(float) * B, &d_ratio), "uwip_malloc");
@@ -185,6 +193,87 @@ int main(int argc, char **argv)
             }
             return true;
         };
+        if (streams) {
+            uwip_pipe_streams_config sc;
+            uwip_pipe_streams_config_default(&sc);
+            sc.format = std::strcmp(ext, "png") == 0 ? UWIP_STREAM_PNG : UWIP_STREAM_JPEG;
+            sc.emit = kf ? UWIP_EMIT_KEYFRAMES : UWIP_EMIT_ALL;
+            CK(uwip_pipe_streams(pipe, &sc), "uwip_pipe_streams");
+            std::vector<uwip_stream_out> outs(B + 1);
+            std::vector<uint8_t> blob(fbytes * (B + 1));
+            std::vector<float> ratio(B);
+            // queue step k: its compressed frames are copied inside the call, so one set of buffers serves every step
+            auto submit = [&](size_t k, uint64_t *ticket) -> int {
+                for (int j = 0; j < B; ++j) {
+                    const size_t i = std::min(k * B + j, n - 1);
+                    if (is_avi) { jptr[j] = &video.buf[video.frames[i].first]; jlen[j] = video.frames[i].second; }
+                    else {
+                        if (!imgio::read_file(frames[i], jfiles[j])) { std::printf("cannot read frame %zu\n", i); return UWIP_ERR_INVALID; }
+                        jptr[j] = jfiles[j].data(); jlen[j] = jfiles[j].size();
+                    }
+                }
+                if (k + 1 == nb) {                      // the padding of the last batch is no frame of the stream
+                    const int rce = uwip_pipe_end_of_stream(pipe, (int)(n - k * B));
+                    if (rce) return rce;
+                }
+                return uwip_pipe_step_streams(pipe, jptr.data(), jlen.data(), B, ticket);
+            };
+            // collect step k (the only wait, and for that step alone) and write its files and report rows
+            auto drain = [&](size_t k, uint64_t ticket) -> int {
+                int nouts = 0;
+                size_t nblob = 0;
+                int rcd = uwip_pipe_result_params(pipe, ticket, bs.data(), cl.data());
+                if (!rcd) rcd = uwip_pipe_collect(pipe, ticket, jstatus.data(), ratio.data(), outs.data(), B + 1, &nouts, blob.data(), blob.size(), &nblob);
+                if (rcd) return rcd;
+                for (int j = 0; j < B && k * B + j < n; ++j)
+                    if (jstatus[j] != 0) {
+                        std::printf("\nframe %zu: device decoder status %d; --streams has no host fallback, run without it\n", k * B + j, jstatus[j]);
+                        return UWIP_ERR_UNSUPPORTED;
+                    }
+                for (int e = 0; e < nouts; ++e) {
+                    char name[512];
+                    std::snprintf(name, sizeof name, "%s%04d.%s", OutputFile.c_str(), outs[e].index, ext);
+                    if (outs[e].size < 0) {
+                        std::printf("\nframe %d: its stream (%lld bytes) exceeds the slot; run without --streams\n", outs[e].index, (long long)-outs[e].size);
+                        return UWIP_ERR_UNSUPPORTED;
+                    }
+                    FILE *jf = std::fopen(name, "wb");
+                    const bool written = jf && std::fwrite(blob.data() + outs[e].offset, 1, (size_t)outs[e].size, jf) == (size_t)outs[e].size;
+                    if (jf) std::fclose(jf);
+                    if (!written) { std::printf("cannot write %s\n", name); return UWIP_ERR_INVALID; }
+                }
+                for (int j = 0; j < B && k * B + j < n; ++j) {
+                    const size_t i = k * B + j;
+                    char name[512];
+                    std::snprintf(name, sizeof name, "%s%04zu.%s", OutputFile.c_str(), i, ext);
+                    report << i << "\t" << name << "\t" << ratio[j] << "\t" << bs[j] << "\t" << cl[j] << "\n";
+                }
+                return UWIP_OK;
+            };
+            uint64_t tk[2] = {0, 0};
+            for (size_t k = 0; k < nb; ++k) {
+                CK(submit(k, &tk[k & 1]), "uwip_pipe_step_streams");
+                if (k) CK(drain(k - 1, tk[(k - 1) & 1]), "uwip_pipe_collect");
+                const bool more = k + 1 < nb;
+                if (!more) CK(drain(k, tk[k & 1]), "uwip_pipe_collect");
+                // the rows of the report: read as rarely as the ring allows (each read drains the stream), and after the last step
+                const bool read_rows = kf && ((k + 1) % kread == 0 || !more);
+                for (int got = (int)krows.size(); read_rows && got == (int)krows.size();) {
+                    CK(uwip_pipe_keyframes(pipe, krows.data(), (int)krows.size(), &got), "uwip_pipe_keyframes");
+                    for (int r = 0; r < got; ++r) {
+                        const uwip_keyframe_row &w = krows[r];
+                        char name[512];
+                        std::snprintf(name, sizeof name, "%s%04d.%s", OutputFile.c_str(), w.index, ext);
+                        if (w.id == 0) kreport << "0\t0\t" << name << "\t0.0\t0.0\n";              // main.cpp:297
+                        else kreport << w.id << "\t" << w.frame << "\t" << name << "\t" << w.overlap << "\t" << w.blur << "\n";   // :381
+                    }
+                }
+                std::printf("\rbatch %zu / %zu", k + 1, nb);
+                std::fflush(stdout);
+            }
+            std::printf("\nEnd of input.\n");
+            goto fail;                                  // rc == 0: the common clean-up
+        }
         if (!device_decode && !fill(0, h_in[0])) { rc = UWIP_ERR_INVALID; what = "reading the input"; goto fail; }
         for (size_t k = 0; k < nb; ++k) {
             const bool more = k + 1 < nb;

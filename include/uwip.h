@@ -729,6 +729,66 @@ int uwip_png_decode(uwip_ctx *ctx, const uint8_t *const *h_streams, const size_t
 int uwip_png_decode_host(uwip_ctx *ctx, const uint8_t *const *h_streams, const size_t *h_sizes, int n, const uwip_batch_u8 *out,
                          const uwip_png_decode_opts *opts, int32_t *h_status);
 
+/* ---- the pipe on files: compressed frames in, compressed (key) frames out, no host wait ----------------------------------
+ * A step that takes a batch of .jpg / .png streams and later hands back the finished .jpg / .png streams of exactly the frames
+ * asked for -- every good frame (UWIP_EMIT_ALL) or the key frames whose rows closed in that step (UWIP_EMIT_KEYFRAMES) -- so that
+ * only compressed bytes cross the link.  Decode, the four stages, the selection of the frames, the gather of their pixels, the
+ * encoders and the packing of the streams are queued on the context's stream; nothing waits for the walker's decisions
+ * (DESIGN.md 7c).
+ * uwip_pipe_streams_config: format UWIP_STREAM_JPEG / UWIP_STREAM_PNG; quality as uwip_jpeg_encode clamps it, 0 means 95;
+ *   png_filter -1..4 as uwip_png_encode; emit UWIP_EMIT_ALL / UWIP_EMIT_KEYFRAMES; slot_bytes per emitted frame, 0 = the raw
+ *   frame size rows * cols * 3; depth = the steps whose results stay collectable, >= 2.  uwip_pipe_streams_config_default: JPEG,
+ *   95, -1, UWIP_EMIT_ALL, 0, 2.
+ * uwip_pipe_streams: before the first step or right after uwip_pipe_reset; allocates what the mode needs (it waits for the
+ *   stream).  UWIP_EMIT_KEYFRAMES on a pipe that is not in key-frame mode (uwip_pipe_keyframe_chain comes first) is
+ *   UWIP_ERR_INVALID.  A pipe that has been given a streams configuration takes its steps of one stream through
+ *   uwip_pipe_step_streams only: the raw-pixel entries do not feed the carried frame.
+ * uwip_pipe_step_streams: n must be the pipe's `frames`.  JPEG and PNG inputs may be mixed: they are told apart by the PNG
+ *   signature, run by run.  The call parses the streams and copies them through the decoders' staging (uwip_jpeg_decode /
+ *   uwip_png_decode), so the caller's buffers are free when it returns; it then queues decode -> the four stages -> selection ->
+ *   encode -> pack and returns without waiting for the device.  *ticket names the step's result.  The throttle (max_in_flight)
+ *   applies as in uwip_pipe_step.  Results live in `depth` slots used in turn: a step whose slot still holds a result that has
+ *   not been collected is refused with UWIP_ERR_INVALID (nothing is queued), not silently lost.  uwip_pipe_end_of_stream,
+ *   uwip_pipe_keyframes, uwip_pipe_last_params and uwip_pipe_reset keep their meaning; after uwip_pipe_end_of_stream(valid) only
+ *   the first `valid` frames of the step are emitted under UWIP_EMIT_ALL (the padding is not a frame of the stream).
+ *   A frame with a negative decoder status is zero-filled on the device before the chain, so the step is deterministic; its
+ *   status is reported, and under UWIP_EMIT_ALL it is not emitted (no entry, no bytes); its neighbours are untouched.  A caller
+ *   that wants a host fallback decodes the frame itself and uses the raw-pixel entries.
+ * uwip_pipe_collect: the only call that waits, and only for that step.  h_status [frames]: the decoders' statuses; h_ratio
+ *   [frames] (may be NULL): the step's ratios (uwip_pipe_step's d_ratio); h_outs [cap]: one uwip_stream_out per emitted frame
+ *   -- `index` the 0-based stream index of the frame, `row_id` the key-frame row's ID (-1 with UWIP_EMIT_ALL), `size` its bytes
+ *   or -(needed) when the stream outgrew its slot (such a frame is absent from the blob), `offset` its position in the blob --
+ *   in row order (key frames) or frame order (all); *n_outs their number (at most frames + 1).  h_blob receives the emitted
+ *   streams back to back, *blob_bytes of them.  When cap or blob_cap is too small the call fails with UWIP_ERR_INVALID, reports
+ *   *n_outs and *blob_bytes, and the result stays collectable.  A result can be collected once.
+ * uwip_pipe_result_params: (BS, CL) the aclahe stage chose in the step `ticket` names, h_bs / h_cl [frames]; waits for that step
+ *   only (uwip_pipe_last_params gives the most recent step's and waits for the stream).  Before the result is collected.
+ * The stream of an emitted frame is byte for byte what uwip_jpeg_encode / uwip_png_encode give for that enhanced frame with the
+ * same quality / filter and slot. */
+#define UWIP_STREAM_JPEG    0
+#define UWIP_STREAM_PNG     1
+#define UWIP_EMIT_ALL       0
+#define UWIP_EMIT_KEYFRAMES 1
+typedef struct uwip_pipe_streams_config {
+    int32_t format;        /* UWIP_STREAM_JPEG / UWIP_STREAM_PNG */
+    int32_t quality;       /* JPEG: 1..100 (clamped), 0 = 95 */
+    int32_t png_filter;    /* PNG: -1 adaptive, 0..4 */
+    int32_t emit;          /* UWIP_EMIT_ALL / UWIP_EMIT_KEYFRAMES */
+    size_t  slot_bytes;    /* per emitted frame; 0 = rows * cols * 3 */
+    int32_t depth;         /* >= 2 */
+    int32_t reserved;      /* 0 */
+} uwip_pipe_streams_config;
+typedef struct uwip_stream_out {        /* 24 bytes */
+    int32_t index, row_id;
+    int64_t size, offset;
+} uwip_stream_out;
+int uwip_pipe_streams_config_default(uwip_pipe_streams_config *cfg);
+int uwip_pipe_streams(uwip_pipe *p, const uwip_pipe_streams_config *cfg);
+int uwip_pipe_step_streams(uwip_pipe *p, const uint8_t *const *h_streams, const size_t *h_sizes, int n, uint64_t *ticket);
+int uwip_pipe_collect(uwip_pipe *p, uint64_t ticket, int32_t *h_status, float *h_ratio, uwip_stream_out *h_outs, int cap,
+                      int *n_outs, uint8_t *h_blob, size_t blob_cap, size_t *blob_bytes);
+int uwip_pipe_result_params(uwip_pipe *p, uint64_t ticket, int32_t *h_bs, int32_t *h_cl);
+
 #ifdef __cplusplus
 }
 #endif

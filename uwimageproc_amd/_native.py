@@ -84,6 +84,19 @@ class KeyframeRow(C.Structure):
                 ("reserved", C.c_int32 * 3)]
 
 
+class PipeStreamsConfig(C.Structure):
+    """Mirror of ``uwip_pipe_streams_config``."""
+
+    _fields_ = [("format", C.c_int32), ("quality", C.c_int32), ("png_filter", C.c_int32), ("emit", C.c_int32),
+                ("slot_bytes", C.c_size_t), ("depth", C.c_int32), ("reserved", C.c_int32)]
+
+
+class StreamOut(C.Structure):
+    """Mirror of ``uwip_stream_out`` (24 bytes)."""
+
+    _fields_ = [("index", C.c_int32), ("row_id", C.c_int32), ("size", C.c_int64), ("offset", C.c_int64)]
+
+
 # uwip_keyframe_chain_host's callbacks
 KF_OVERLAP_FN = C.CFUNCTYPE(C.c_float, C.c_void_p, C.c_int32, C.c_int32)
 KF_BLUR_FN = C.CFUNCTYPE(C.c_float, C.c_void_p, C.c_int32)
@@ -187,6 +200,12 @@ SIGNATURES = {
     "uwip_pipe_keyframes": (C.c_int, [_P, C.POINTER(KeyframeRow), C.c_int, C.POINTER(C.c_int)]),
     "uwip_keyframe_chain_host": (C.c_int, [C.POINTER(KeyframeConfig), C.c_int, C.c_int, KF_OVERLAP_FN, KF_BLUR_FN, _P,
                                            C.POINTER(KeyframeRow), C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int32)]),
+    "uwip_pipe_streams_config_default": (C.c_int, [C.POINTER(PipeStreamsConfig)]),
+    "uwip_pipe_streams": (C.c_int, [_P, C.POINTER(PipeStreamsConfig)]),
+    "uwip_pipe_step_streams": (C.c_int, [_P, _P, _P, C.c_int, C.POINTER(C.c_uint64)]),
+    "uwip_pipe_collect": (C.c_int, [_P, C.c_uint64, C.POINTER(C.c_int32), C.POINTER(C.c_float), C.POINTER(StreamOut), C.c_int,
+                                    C.POINTER(C.c_int), _P, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "uwip_pipe_result_params": (C.c_int, [_P, C.c_uint64, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "uwip_jpeg_bound": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
     "uwip_jpeg_encode": (C.c_int, [_P, _B, C.c_int, _P, C.c_size_t, _P]),
     "uwip_jpeg_encode_host": (C.c_int, [_P, _B, C.c_int, _P, C.c_size_t, _P]),

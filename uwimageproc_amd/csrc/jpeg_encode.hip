@@ -78,9 +78,10 @@ __device__ __forceinline__ int block_prev(const Geo &g, int b)
 }
 
 __global__ __launch_bounds__(256) void k_jpeg_transform(const uint8_t *__restrict__ img, Geo g, const JpegConst *__restrict__ cst,
-                                                        int16_t *__restrict__ coef)
+                                                        int16_t *__restrict__ coef, const int32_t *__restrict__ nsel = nullptr)
 {
     __shared__ int32_t s_qv[2][64];
+    if (nsel && (int)blockIdx.y >= *nsel) return;                        // uniform over the workgroup, ahead of every barrier
     if (threadIdx.x < 128) s_qv[threadIdx.x >> 6][threadIdx.x & 63] = cst->qv[threadIdx.x >> 6][threadIdx.x & 63];
     __syncthreads();
     const int b = blockIdx.x * 256 + threadIdx.x, f = blockIdx.y;
@@ -192,9 +193,11 @@ __device__ __forceinline__ void code_block(const int16_t *__restrict__ coef, con
 }
 
 __global__ __launch_bounds__(kBitsWG) void k_jpeg_bits(const int16_t *__restrict__ coef, Geo g, const JpegHuff *__restrict__ huff,
-                                                       uint32_t *__restrict__ blkoff, uint32_t *__restrict__ wgsum, int nwg)
+                                                       uint32_t *__restrict__ blkoff, uint32_t *__restrict__ wgsum, int nwg,
+                                                       const int32_t *__restrict__ nsel = nullptr)
 {
     __shared__ uint32_t s_dc[2][16], s_ac[2][256], s_scan[8];
+    if (nsel && (int)blockIdx.y >= *nsel) return;
     load_huff(huff, s_dc, s_ac);
     __syncthreads();
     const int b = blockIdx.x * kBitsWG + threadIdx.x, f = blockIdx.y;
@@ -222,10 +225,11 @@ __device__ uint64_t scan_excl_u64(const uint32_t *__restrict__ in, uint64_t *__r
 }
 
 __global__ __launch_bounds__(256) void k_jpeg_scan_bits(const uint32_t *__restrict__ wgsum, uint64_t *__restrict__ wgbase,
-                                                        uint64_t *__restrict__ totbits, int nwg)
+                                                        uint64_t *__restrict__ totbits, int nwg, const int32_t *__restrict__ nsel = nullptr)
 {
     __shared__ uint32_t s_scan[8];
     const int f = blockIdx.x;
+    if (nsel && f >= *nsel) return;
     const uint64_t t = scan_excl_u64(wgsum + (size_t)f * nwg, wgbase + (size_t)f * nwg, nwg, s_scan);
     if (threadIdx.x == 0) totbits[f] = t;
 }
@@ -249,10 +253,11 @@ __device__ __forceinline__ bool stores(uint64_t totbits, uint32_t hdr_len, size_
 
 // zero the words two emit workgroups share, ahead of their atomicOr
 __global__ void k_jpeg_zero_shared(Geo g, Offs o, const JpegConst *__restrict__ cst, size_t slot_bytes, uint32_t *__restrict__ ubuf,
-                                   size_t ustride, int nwg_emit)
+                                   size_t ustride, int nwg_emit, const int32_t *__restrict__ nsel = nullptr)
 {
     const int w = blockIdx.x * blockDim.x + threadIdx.x, f = blockIdx.y;
     if (w < 1 || w >= nwg_emit) return;
+    if (nsel && f >= *nsel) return;
     if (!stores(o.totbits[f], cst->hdr_len, slot_bytes)) return;
     const uint64_t o0 = bit_offset(o, g, f, w * kEmitWG);
     if (o0 & 31) ubuf[(size_t)f * ustride + (size_t)(o0 >> 5)] = 0u;
@@ -261,9 +266,10 @@ __global__ void k_jpeg_zero_shared(Geo g, Offs o, const JpegConst *__restrict__ 
 __global__ __launch_bounds__(kEmitWG) void k_jpeg_emit(const int16_t *__restrict__ coef, Geo g, const JpegHuff *__restrict__ huff, Offs o,
                                                        const JpegConst *__restrict__ cst, size_t slot_bytes,
                                                        uint32_t *__restrict__ ubuf, size_t ustride, uint32_t *__restrict__ ffemit,
-                                                       uint32_t *__restrict__ notff, int nwg_emit)
+                                                       uint32_t *__restrict__ notff, int nwg_emit, const int32_t *__restrict__ nsel = nullptr)
 {
     __shared__ uint32_t s_dc[2][16], s_ac[2][256], s_win[kWinWords], s_cnt;
+    if (nsel && (int)blockIdx.y >= *nsel) return;
     load_huff(huff, s_dc, s_ac);
     const int w = blockIdx.x, f = blockIdx.y;
     const int b0 = w * kEmitWG, b1 = min(b0 + kEmitWG, g.nblk);
@@ -341,10 +347,11 @@ __device__ __forceinline__ uint32_t chunk_ff(const uint32_t *__restrict__ ubuf_f
 
 __global__ __launch_bounds__(256) void k_jpeg_ffcount(const uint32_t *__restrict__ ubuf, size_t ustride, const uint64_t *__restrict__ totbits,
                                                       const JpegConst *__restrict__ cst, size_t slot_bytes, uint32_t *__restrict__ chunkcnt,
-                                                      int nchunk)
+                                                      int nchunk, const int32_t *__restrict__ nsel = nullptr)
 {
     __shared__ uint32_t s_scan[8];
     const int c = blockIdx.x, f = blockIdx.y;
+    if (nsel && f >= *nsel) return;
     const uint64_t tb = totbits[f], ubytes = (tb + 7) / 8;
     const uint64_t s = (uint64_t)c * kChunk + threadIdx.x * 16;
     uint32_t cnt = 0;
@@ -359,10 +366,12 @@ __global__ __launch_bounds__(256) void k_jpeg_ffcount(const uint32_t *__restrict
 // per frame: scan of the chunk counts, and the stream length from the emit pass's count
 __global__ __launch_bounds__(256) void k_jpeg_finish(const uint32_t *__restrict__ chunkcnt, uint64_t *__restrict__ chunkbase, int nchunk, Geo g,
                                                      Offs o, const JpegConst *__restrict__ cst, const uint32_t *__restrict__ ffemit,
-                                                     const uint32_t *__restrict__ notff, int nwg_emit, int64_t *__restrict__ needed)
+                                                     const uint32_t *__restrict__ notff, int nwg_emit, int64_t *__restrict__ needed,
+                                                     const int32_t *__restrict__ nsel = nullptr)
 {
     __shared__ uint32_t s_scan[8];
     const int f = blockIdx.x;
+    if (nsel && f >= *nsel) return;
     (void)scan_excl_u64(chunkcnt + (size_t)f * nchunk, chunkbase + (size_t)f * nchunk, nchunk, s_scan);
     uint32_t cnt = 0;
     for (int w = 1 + (int)threadIdx.x; w < nwg_emit; w += 256)
@@ -375,10 +384,14 @@ __global__ __launch_bounds__(256) void k_jpeg_finish(const uint32_t *__restrict_
 __global__ __launch_bounds__(256) void k_jpeg_assemble(const uint32_t *__restrict__ ubuf, size_t ustride, const uint64_t *__restrict__ totbits,
                                                        const uint64_t *__restrict__ chunkbase, int nchunk, const JpegConst *__restrict__ cst,
                                                        const int64_t *__restrict__ needed, uint8_t *__restrict__ streams, size_t slot_bytes,
-                                                       int64_t *__restrict__ sizes)
+                                                       int64_t *__restrict__ sizes, const int32_t *__restrict__ nsel = nullptr)
 {
     __shared__ uint32_t s_scan[8];
     const int c = blockIdx.x, f = blockIdx.y;
+    if (nsel && f >= *nsel) {                                            // not selected: size 0, nothing written
+        if (c == 0 && threadIdx.x == 0) sizes[f] = 0;
+        return;
+    }
     const int64_t need = needed[f];
     const bool fits = (uint64_t)need <= (uint64_t)slot_bytes;
     if (c == 0 && threadIdx.x == 0) sizes[f] = fits ? need : -need;
@@ -440,6 +453,12 @@ UWIP_API size_t uwip_jpeg_bound(int rows, int cols, int channels)
 
 UWIP_API int uwip_jpeg_encode(uwip_ctx *ctx, const uwip_batch_u8 *frames, int quality, uint8_t *d_streams, size_t slot_bytes,
                               int64_t *d_sizes)
+{
+    return uwip_jpeg_encode_dev(ctx, frames, quality, d_streams, slot_bytes, d_sizes, nullptr);
+}
+
+int uwip_jpeg_encode_dev(uwip_ctx *ctx, const uwip_batch_u8 *frames, int quality, uint8_t *d_streams, size_t slot_bytes,
+                         int64_t *d_sizes, const int32_t *d_count)
 {
     int rc = uwip_check_batch(ctx, frames, 0);
     if (rc) return rc;
@@ -508,38 +527,38 @@ UWIP_API int uwip_jpeg_encode(uwip_ctx *ctx, const uwip_batch_u8 *frames, int qu
     const uint8_t *img = static_cast<const uint8_t *>(frames->data);
     {
         uwip_kscope ks(ctx, "k_jpeg_transform");
-        k_jpeg_transform<<<dim3(nwg_bits, F), 256, 0, ctx->stream>>>(img, g, cst, coef);
+        k_jpeg_transform<<<dim3(nwg_bits, F), 256, 0, ctx->stream>>>(img, g, cst, coef, d_count);
     }
     {
         uwip_kscope ks(ctx, "k_jpeg_bits");
-        k_jpeg_bits<<<dim3(nwg_bits, F), kBitsWG, 0, ctx->stream>>>(coef, g, huff, blkoff, wgsum, nwg_bits);
+        k_jpeg_bits<<<dim3(nwg_bits, F), kBitsWG, 0, ctx->stream>>>(coef, g, huff, blkoff, wgsum, nwg_bits, d_count);
     }
     {
         uwip_kscope ks(ctx, "k_jpeg_scan_bits");
-        k_jpeg_scan_bits<<<F, 256, 0, ctx->stream>>>(wgsum, wgbase, totbits, nwg_bits);
+        k_jpeg_scan_bits<<<F, 256, 0, ctx->stream>>>(wgsum, wgbase, totbits, nwg_bits, d_count);
     }
     {
         uwip_kscope ks(ctx, "k_jpeg_zero_shared");
         k_jpeg_zero_shared<<<dim3(uwip_cdiv((size_t)nwg_emit, 256), F), 256, 0, ctx->stream>>>(g, o, cst, slot_bytes, ubuf, ustride,
-                                                                                               nwg_emit);
+                                                                                               nwg_emit, d_count);
     }
     {
         uwip_kscope ks(ctx, "k_jpeg_emit");
         k_jpeg_emit<<<dim3(nwg_emit, F), kEmitWG, 0, ctx->stream>>>(coef, g, huff, o, cst, slot_bytes, ubuf, ustride, ffemit, notff,
-                                                                    nwg_emit);
+                                                                    nwg_emit, d_count);
     }
     {
         uwip_kscope ks(ctx, "k_jpeg_ffcount");
-        k_jpeg_ffcount<<<dim3(nchunk, F), 256, 0, ctx->stream>>>(ubuf, ustride, totbits, cst, slot_bytes, chunkcnt, nchunk);
+        k_jpeg_ffcount<<<dim3(nchunk, F), 256, 0, ctx->stream>>>(ubuf, ustride, totbits, cst, slot_bytes, chunkcnt, nchunk, d_count);
     }
     {
         uwip_kscope ks(ctx, "k_jpeg_finish");
-        k_jpeg_finish<<<F, 256, 0, ctx->stream>>>(chunkcnt, chunkbase, nchunk, g, o, cst, ffemit, notff, nwg_emit, needed);
+        k_jpeg_finish<<<F, 256, 0, ctx->stream>>>(chunkcnt, chunkbase, nchunk, g, o, cst, ffemit, notff, nwg_emit, needed, d_count);
     }
     {
         uwip_kscope ks(ctx, "k_jpeg_assemble");
         k_jpeg_assemble<<<dim3(nchunk, F), 256, 0, ctx->stream>>>(ubuf, ustride, totbits, chunkbase, nchunk, cst, needed, d_streams,
-                                                                  slot_bytes, d_sizes);
+                                                                  slot_bytes, d_sizes, d_count);
     }
     UWIP_HIP(ctx, hipGetLastError());
     return UWIP_OK;

@@ -5,6 +5,7 @@
 // calls the library's own entry points; what it adds is the state the chain carries between steps (rounds 1-4 kept that in
 // Python, uwimageproc_amd/pipeline.py): the feature-slot carry, the throttle, the double-buffered host front end.
 #include "uwip_internal.hpp"
+#include "pipe_streams.hpp"
 #include <cstring>
 #include <deque>
 
@@ -52,6 +53,27 @@ struct uwip_pipe {
         uwip_keyframe_row *ring = nullptr;
         uint8_t *res = nullptr;                        // the batch at the working size (calcBlur's input, main.cpp:311)
     } kf;
+    // compressed frames in, compressed (key) frames out (uwip_pipe_streams; pipe_streams.hip)
+    struct Streams {
+        bool on = false;
+        uwip_pipe_streams_config sc{};
+        size_t slot_bytes = 0, one_frame = 0, table_bytes = 0;
+        int32_t base = 0;                              // predecessor mode: stream index of the next step's frame 0
+        uint64_t k = 0;                                // steps taken; ticket = step number, 1-based
+        uint8_t *block = nullptr;                      // one device allocation for everything below
+        uint8_t *src = nullptr, *work = nullptr;       // [F] decoded / enhanced frames
+        uint8_t *carried = nullptr, *compact = nullptr;// one frame; [F + 1] frames
+        uint8_t *slots = nullptr;                      // [F + 1][slot_bytes]
+        int64_t *sizes = nullptr;                      // [F + 1]
+        int32_t *status = nullptr, *sel_n = nullptr;
+        uint32_t *emitted = nullptr;                   // rows of the walker's ring already handed out
+        float *ratio = nullptr;
+        uwip_ps::Sel *sel = nullptr;
+        std::vector<uint8_t *> table, blob;            // [depth] device
+        std::vector<uint8_t *> h_table;                // [depth] page-locked host
+        std::vector<uint64_t> t_table, ticket;         // [depth] the table's download; the step whose result the slot holds (0: free)
+        std::vector<std::vector<int32_t>> h_par;       // [depth] the step's (BS, CL) where the host made the choice (else empty)
+    } st;
 
     int fail(int code, const char *what)
     {
@@ -191,14 +213,50 @@ void kf_free(uwip_pipe *p)
     p->kf = uwip_pipe::Keyframe();
 }
 
+void st_free(uwip_pipe *p)
+{
+    uwip_free(p->ctx, p->st.block);
+    for (uint8_t *h : p->st.h_table) uwip_host_free(p->ctx, h);
+    p->st = uwip_pipe::Streams();
+}
+
+int ensure_copier(uwip_pipe *p)
+{
+    if (p->copier) return UWIP_OK;
+    int rc = uwip_copier_create(p->ctx->device, &p->copier);
+    if (rc) return p->fail(rc, "uwip_copier_create failed");
+    p->own_copier = true;
+    return UWIP_OK;
+}
+
+// Nothing in a step waits on the host, so a caller that loops would queue steps without bound and end up spinning inside
+// the runtime once its hardware queue is full: the wait for the oldest queued step polls its event and sleeps in between.
+int throttle_wait(uwip_pipe *p)
+{
+    while ((int)p->inflight.size() >= p->cfg.max_in_flight) {
+        hipEvent_t e = p->inflight.front();
+        const hipError_t he = uwip_event_wait(e, 1000);
+        if (he != hipSuccess) return p->fail(UWIP_ERR_HIP, hipGetErrorString(he));
+        p->inflight.pop_front();
+        p->ev_pool.push_back(e);
+    }
+    return UWIP_OK;
+}
+
+int throttle_record(uwip_pipe *p)
+{
+    hipEvent_t e = nullptr;
+    if (!p->ev_pool.empty()) { e = p->ev_pool.back(); p->ev_pool.pop_back(); }
+    else if (hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess) return p->fail(UWIP_ERR_HIP, "hipEventCreate");
+    if (hipEventRecord(e, p->ctx->stream) != hipSuccess) { p->ev_pool.push_back(e); return p->fail(UWIP_ERR_HIP, "hipEventRecord"); }
+    p->inflight.push_back(e);
+    return UWIP_OK;
+}
+
 int ensure_host_state(uwip_pipe *p)
 {
     const uwip_pipe_config &c = p->cfg;
-    if (!p->copier) {
-        int rc = uwip_copier_create(p->ctx->device, &p->copier);
-        if (rc) return p->fail(rc, "uwip_copier_create failed");
-        p->own_copier = true;
-    }
+    if (int rc = ensure_copier(p)) return rc;
     if (!p->src[0]) {
         uint8_t *base = (uint8_t *)c.d_staging;
         if (!base) {
@@ -301,6 +359,9 @@ UWIP_API int uwip_pipe_sync(uwip_pipe *p)
             for (uint64_t x : t)
                 if (x && (rc = uwip_copier_wait(p->copier, x))) return copier_rc(p, rc);
         }
+    if (p->copier)
+        for (uint64_t x : p->st.t_table)
+            if (x && (rc = uwip_copier_wait(p->copier, x))) return copier_rc(p, rc);
     return UWIP_OK;
 }
 
@@ -314,6 +375,7 @@ UWIP_API int uwip_pipe_destroy(uwip_pipe *p)
     if (p->own_staging) uwip_free(p->ctx, p->staging);
     uwip_features_destroy(p->feats);
     kf_free(p);
+    st_free(p);
     uwip_free(p->ctx, p->v);
     delete p;
     return UWIP_OK;
@@ -341,23 +403,10 @@ UWIP_API int uwip_pipe_step(uwip_pipe *p, const uwip_batch_u8 *in, const uwip_ba
 {
     if (!p) return UWIP_ERR_INVALID;
     if (int rc_e = uwip_enter(p->ctx)) return p->from_ctx(rc_e);
-    // Nothing in a step waits on the host, so a caller that loops would queue steps without bound and end up spinning inside
-    // the runtime once its hardware queue is full: the wait for the oldest queued step polls its event and sleeps in between.
-    while ((int)p->inflight.size() >= p->cfg.max_in_flight) {
-        hipEvent_t e = p->inflight.front();
-        const hipError_t he = uwip_event_wait(e, 1000);
-        if (he != hipSuccess) return p->fail(UWIP_ERR_HIP, hipGetErrorString(he));
-        p->inflight.pop_front();
-        p->ev_pool.push_back(e);
-    }
-    int rc = uwip_pipe_stages(p, UWIP_PIPE_ALL, in, out, d_ratio, d_info);
+    int rc = throttle_wait(p);
     if (rc) return rc;
-    hipEvent_t e = nullptr;
-    if (!p->ev_pool.empty()) { e = p->ev_pool.back(); p->ev_pool.pop_back(); }
-    else if (hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess) return p->fail(UWIP_ERR_HIP, "hipEventCreate");
-    if (hipEventRecord(e, p->ctx->stream) != hipSuccess) { p->ev_pool.push_back(e); return p->fail(UWIP_ERR_HIP, "hipEventRecord"); }
-    p->inflight.push_back(e);
-    return UWIP_OK;
+    if ((rc = uwip_pipe_stages(p, UWIP_PIPE_ALL, in, out, d_ratio, d_info))) return rc;
+    return throttle_record(p);
 }
 
 UWIP_API int uwip_pipe_step_host(uwip_pipe *p, const void *h_in, void *h_out, float *h_ratio, const void *h_prefetch, uint64_t tickets[3])
@@ -418,6 +467,7 @@ UWIP_API int uwip_pipe_reset(uwip_pipe *p)
     p->eos_valid = -1;
     p->kf.started = false;
     p->kf.base = 0;
+    p->st.base = 0;
     return UWIP_OK;
 }
 
@@ -505,6 +555,8 @@ UWIP_API int uwip_pipe_keyframe_chain(uwip_pipe *p, const uwip_keyframe_config *
         return p->from_ctx(rc);
     }
     k.on = true;
+    // a streams configuration made earlier counts the rows of the new ring (State::total starts at 0 again)
+    if (p->st.on && hipMemsetAsync(p->st.emitted, 0, sizeof(uint32_t), p->ctx->stream) != hipSuccess) return p->fail(UWIP_ERR_HIP, "hipMemsetAsync");
     return UWIP_OK;
 }
 
@@ -550,5 +602,206 @@ UWIP_API int uwip_pipe_keyframes(uwip_pipe *p, uwip_keyframe_row *h_rows, int ca
     }
     k.consumed += m;
     *n = (int)m;
+    return UWIP_OK;
+}
+
+// ---- compressed frames in, compressed (key) frames out ----------------------------------------------------------------
+
+UWIP_API int uwip_pipe_streams_config_default(uwip_pipe_streams_config *cfg)
+{
+    if (!cfg) return UWIP_ERR_INVALID;
+    std::memset(cfg, 0, sizeof *cfg);
+    cfg->format = UWIP_STREAM_JPEG;
+    cfg->quality = 95;                          // cv::imwrite's default
+    cfg->png_filter = -1;
+    cfg->emit = UWIP_EMIT_ALL;
+    cfg->slot_bytes = 0;                        // the raw frame size
+    cfg->depth = 2;
+    return UWIP_OK;
+}
+
+UWIP_API int uwip_pipe_streams(uwip_pipe *p, const uwip_pipe_streams_config *cfg)
+{
+    if (!p) return UWIP_ERR_INVALID;
+    if (!cfg) return p->fail(UWIP_ERR_INVALID, "null streams configuration");
+    if (cfg->format != UWIP_STREAM_JPEG && cfg->format != UWIP_STREAM_PNG) return p->fail(UWIP_ERR_INVALID, "format must be UWIP_STREAM_JPEG or UWIP_STREAM_PNG");
+    if (cfg->emit != UWIP_EMIT_ALL && cfg->emit != UWIP_EMIT_KEYFRAMES) return p->fail(UWIP_ERR_INVALID, "emit must be UWIP_EMIT_ALL or UWIP_EMIT_KEYFRAMES");
+    if (cfg->png_filter < -1 || cfg->png_filter > 4) return p->fail(UWIP_ERR_INVALID, "png_filter must be -1 (adaptive) or 0..4");
+    if (cfg->depth < 2 || cfg->depth > 64) return p->fail(UWIP_ERR_INVALID, "depth must be 2..64");
+    if (cfg->emit == UWIP_EMIT_KEYFRAMES && !p->kf.on)
+        return p->fail(UWIP_ERR_INVALID, "UWIP_EMIT_KEYFRAMES needs key-frame mode (uwip_pipe_keyframe_chain first)");
+    if (p->have_prev || p->kf.started || p->eos_valid >= 0 || p->st.base != 0)
+        return p->fail(UWIP_ERR_INVALID, "uwip_pipe_streams: before the first step or right after uwip_pipe_reset");
+    if (int rc_e = uwip_enter(p->ctx)) return p->from_ctx(rc_e);
+    int rc = ensure_copier(p);
+    if (rc) return rc;
+    if ((rc = uwip_pipe_sync(p))) return rc;    // the buffers are re-made; results not collected are dropped
+    st_free(p);
+    uwip_pipe::Streams &s = p->st;
+    const int F = p->cfg.frames, depth = cfg->depth;
+    s.sc = *cfg;
+    if (s.sc.quality == 0) s.sc.quality = 95;
+    s.one_frame = (size_t)p->cfg.rows * p->cfg.cols * 3;
+    s.slot_bytes = cfg->slot_bytes ? cfg->slot_bytes : s.one_frame;
+    s.table_bytes = uwip_ps::table_bytes(F);
+    const size_t blob_cap = (size_t)(F + 1) * s.slot_bytes;
+    size_t off = 0;
+    auto take = [&](size_t bytes) { const size_t at = off; off += align256(bytes); return at; };
+    const size_t o_src = take(s.one_frame * F), o_work = take(s.one_frame * F), o_carried = take(s.one_frame),
+                 o_compact = take(s.one_frame * (F + 1)), o_slots = take(blob_cap + 16), o_sizes = take(8 * (size_t)(F + 1)),
+                 o_status = take(4 * (size_t)F), o_seln = take(4), o_emitted = take(4), o_ratio = take(4 * (size_t)F),
+                 o_sel = take(sizeof(uwip_ps::Sel) * (size_t)(F + 1));
+    std::vector<size_t> o_table(depth), o_blob(depth);
+    for (int d = 0; d < depth; ++d) { o_table[d] = take(s.table_bytes); o_blob[d] = take(blob_cap + 16); }
+    void *dv = nullptr;
+    if ((rc = uwip_malloc(p->ctx, off, &dv))) return p->from_ctx(rc);
+    uint8_t *b = (uint8_t *)dv;
+    s.block = b;
+    s.src = b + o_src; s.work = b + o_work; s.carried = b + o_carried; s.compact = b + o_compact; s.slots = b + o_slots;
+    s.sizes = (int64_t *)(b + o_sizes); s.status = (int32_t *)(b + o_status); s.sel_n = (int32_t *)(b + o_seln);
+    s.emitted = (uint32_t *)(b + o_emitted); s.ratio = (float *)(b + o_ratio); s.sel = (uwip_ps::Sel *)(b + o_sel);
+    for (int d = 0; d < depth; ++d) {
+        s.table.push_back(b + o_table[d]);
+        s.blob.push_back(b + o_blob[d]);
+        void *h = nullptr;
+        if ((rc = uwip_host_alloc(p->ctx, s.table_bytes, &h))) { st_free(p); return p->from_ctx(rc); }
+        s.h_table.push_back((uint8_t *)h);
+    }
+    s.t_table.assign(depth, 0);
+    s.ticket.assign(depth, 0);
+    s.h_par.assign(depth, std::vector<int32_t>());
+    // the carried frame is read only by a row that names it, which a carry precedes; zeroed all the same.  The rows the ring
+    // holds by now (none on a new pipe) are not this configuration's to emit.
+    hipError_t he = hipMemsetAsync(s.carried, 0, s.one_frame, p->ctx->stream);
+    if (he == hipSuccess) he = hipMemsetAsync(s.emitted, 0, sizeof(uint32_t), p->ctx->stream);
+    if (he == hipSuccess && p->kf.on)
+        he = hipMemcpyAsync(s.emitted, &p->kf.state->total, sizeof(uint32_t), hipMemcpyDeviceToDevice, p->ctx->stream);
+    if (he != hipSuccess) { st_free(p); return p->fail(UWIP_ERR_HIP, hipGetErrorString(he)); }
+    s.on = true;
+    return UWIP_OK;
+}
+
+UWIP_API int uwip_pipe_step_streams(uwip_pipe *p, const uint8_t *const *h_streams, const size_t *h_sizes, int n, uint64_t *ticket)
+{
+    if (!p) return UWIP_ERR_INVALID;
+    if (!h_streams || !h_sizes || !ticket) return p->fail(UWIP_ERR_INVALID, "null argument");
+    *ticket = 0;
+    if (n != p->cfg.frames) return p->fail(UWIP_ERR_INVALID, "n must be the pipe's `frames`");
+    for (int j = 0; j < n; ++j)
+        if (!h_streams[j] && h_sizes[j]) return p->fail(UWIP_ERR_INVALID, "null stream");
+    if (int rc_e = uwip_enter(p->ctx)) return p->from_ctx(rc_e);
+    uwip_pipe::Streams &s = p->st;
+    if (!s.on) return p->fail(UWIP_ERR_INVALID, "the pipe has no streams configuration (uwip_pipe_streams)");
+    const int F = n, slot = (int)(s.k % (uint64_t)s.sc.depth);
+    if (s.ticket[slot]) return p->fail(UWIP_ERR_INVALID, "the result this step would overwrite has not been collected (uwip_pipe_collect)");
+    uwip_ctx *ctx = p->ctx;
+    int rc = throttle_wait(p);
+    if (rc) return rc;
+    // decode: a step of one kind is one call, a mixed step one call per run of one kind, each into its slots of the batch
+    static const uint8_t png_sig[8] = {137, 80, 78, 71, 13, 10, 26, 10};
+    auto is_png = [&](int j) { return h_sizes[j] >= 8 && !std::memcmp(h_streams[j], png_sig, 8); };
+    const uwip_batch_u8 in = batch_of(s.src, p->cfg, 3), out = batch_of(s.work, p->cfg, 3);
+    for (int j0 = 0; j0 < F;) {
+        int j1 = j0 + 1;
+        while (j1 < F && is_png(j1) == is_png(j0)) ++j1;
+        const uwip_batch_u8 bq = batch_of(s.src + s.one_frame * j0, p->cfg, 3, j1 - j0);
+        rc = is_png(j0) ? uwip_png_decode(ctx, h_streams + j0, h_sizes + j0, j1 - j0, &bq, nullptr, s.status + j0)
+                        : uwip_jpeg_decode(ctx, h_streams + j0, h_sizes + j0, j1 - j0, &bq, nullptr, s.status + j0);
+        if (rc) return p->from_ctx(rc);
+        j0 = j1;
+    }
+    if ((rc = uwip_ps_blank(ctx, s.src, F, s.one_frame, s.status))) return p->from_ctx(rc);
+    // what the selection needs to know of this step, before the overlap stage consumes the end-of-stream mark
+    const bool keyframes = s.sc.emit == UWIP_EMIT_KEYFRAMES;
+    uwip_ps::Step u{};
+    u.emit_all = keyframes ? 0 : 1; u.F = F; u.valid = p->eos_valid >= 0 ? p->eos_valid : F;
+    u.base = p->kf.on ? p->kf.base : s.base;
+    u.max_rows = keyframes ? p->kf.kc.max_rows : 1;
+    u.frame_bytes = s.one_frame; u.status = s.status;
+    u.ring = keyframes ? p->kf.ring : nullptr;
+    u.total = keyframes ? &p->kf.state->total : nullptr;
+    u.carry_best = keyframes ? &p->kf.state->carry_best : nullptr;
+    u.emitted = s.emitted; u.work = s.work; u.carried = s.carried; u.compact = s.compact; u.sel = s.sel; u.sel_n = s.sel_n;
+    const bool last = p->eos_valid >= 0;
+    if ((rc = run_stages(p, UWIP_PIPE_ALL, &in, &out, s.ratio, nullptr))) return rc;
+    p->last_frames = s.work; p->last_ratio = s.ratio; p->last_info = nullptr;
+    s.base = last ? 0 : s.base + F;
+    if ((rc = uwip_ps_select_gather(ctx, u))) return p->from_ctx(rc);
+    const uwip_batch_u8 cb = batch_of(s.compact, p->cfg, 3, F + 1);
+    rc = s.sc.format == UWIP_STREAM_PNG ? uwip_png_encode_dev(ctx, &cb, s.sc.png_filter, s.slots, s.slot_bytes, s.sizes, s.sel_n)
+                                        : uwip_jpeg_encode_dev(ctx, &cb, s.sc.quality, s.slots, s.slot_bytes, s.sizes, s.sel_n);
+    if (rc) return p->from_ctx(rc);
+    // the aclahe stage's parameters go with the result: from the device record where the choice was made there, else from the host's
+    const int32_t *d_par = nullptr;
+    s.h_par[slot].clear();
+    if (ctx->aclahe_last_n == F && ctx->aclahe_last_on_device) {
+        d_par = (const int32_t *)uwip_ws(ctx, "auto.par", sizeof(int32_t) * 4 * (size_t)F);
+        if (!d_par) return p->from_ctx(UWIP_ERR_NOMEM);
+    } else if (ctx->aclahe_last_n == F && ctx->aclahe_last_host.size() == 4 * (size_t)F) {
+        for (int f = 0; f < F; ++f) { s.h_par[slot].push_back(ctx->aclahe_last_host[4 * f]); s.h_par[slot].push_back(ctx->aclahe_last_host[4 * f + 1]); }
+    }
+    if ((rc = uwip_ps_pack(ctx, u, s.sizes, s.ratio, d_par, s.slots, s.slot_bytes, s.table[slot], s.blob[slot]))) return p->from_ctx(rc);
+    // the one small copy of a result, requested now: it leaves when the stream has finished this step
+    if ((rc = uwip_copier_download(p->copier, ctx, s.h_table[slot], s.table[slot], s.table_bytes, &s.t_table[slot]))) return copier_rc(p, rc);
+    s.k += 1;
+    s.ticket[slot] = s.k;
+    *ticket = s.k;
+    return throttle_record(p);
+}
+
+UWIP_API int uwip_pipe_collect(uwip_pipe *p, uint64_t ticket, int32_t *h_status, float *h_ratio, uwip_stream_out *h_outs, int cap,
+                               int *n_outs, uint8_t *h_blob, size_t blob_cap, size_t *blob_bytes)
+{
+    if (!p) return UWIP_ERR_INVALID;
+    if (!h_status || !n_outs || !blob_bytes || cap < 0 || (cap > 0 && !h_outs) || (blob_cap > 0 && !h_blob))
+        return p->fail(UWIP_ERR_INVALID, "null buffer or negative capacity");
+    *n_outs = 0;
+    *blob_bytes = 0;
+    uwip_pipe::Streams &s = p->st;
+    if (!s.on) return p->fail(UWIP_ERR_INVALID, "the pipe has no streams configuration (uwip_pipe_streams)");
+    if (!ticket || ticket > s.k) return p->fail(UWIP_ERR_INVALID, "no such ticket");
+    const int slot = (int)((ticket - 1) % (uint64_t)s.sc.depth), F = p->cfg.frames;
+    if (s.ticket[slot] != ticket) return p->fail(UWIP_ERR_INVALID, "this result has been collected already");
+    if (int rc_e = uwip_enter(p->ctx)) return p->from_ctx(rc_e);
+    int rc = uwip_copier_wait(p->copier, s.t_table[slot]);          // the step is done when its table has arrived
+    if (rc) return copier_rc(p, rc);
+    const uint8_t *t = s.h_table[slot];
+    uwip_ps::TableHdr hdr;
+    std::memcpy(&hdr, t, sizeof hdr);
+    *n_outs = hdr.n_outs;
+    *blob_bytes = (size_t)hdr.blob_bytes;
+    if (hdr.n_outs > cap) return p->fail(UWIP_ERR_INVALID, "h_outs is too small (*n_outs entries are needed); the result stays collectable");
+    if (hdr.blob_bytes > blob_cap) return p->fail(UWIP_ERR_INVALID, "h_blob is too small (*blob_bytes are needed); the result stays collectable");
+    if (hdr.blob_bytes) {
+        uint64_t tb = 0;
+        if ((rc = uwip_copier_download(p->copier, nullptr, h_blob, s.blob[slot], (size_t)hdr.blob_bytes, &tb)) ||
+            (rc = uwip_copier_wait(p->copier, tb)))
+            return copier_rc(p, rc);
+    }
+    std::memcpy(h_outs, t + uwip_ps::outs_offset(), sizeof(uwip_stream_out) * (size_t)hdr.n_outs);
+    std::memcpy(h_status, t + uwip_ps::status_offset(F), sizeof(int32_t) * (size_t)F);
+    if (h_ratio) std::memcpy(h_ratio, t + uwip_ps::ratio_offset(F), sizeof(float) * (size_t)F);
+    s.ticket[slot] = 0;
+    s.t_table[slot] = 0;
+    return UWIP_OK;
+}
+
+UWIP_API int uwip_pipe_result_params(uwip_pipe *p, uint64_t ticket, int32_t *h_bs, int32_t *h_cl)
+{
+    if (!p) return UWIP_ERR_INVALID;
+    if (!h_bs || !h_cl) return p->fail(UWIP_ERR_INVALID, "null output");
+    uwip_pipe::Streams &s = p->st;
+    if (!s.on) return p->fail(UWIP_ERR_INVALID, "the pipe has no streams configuration (uwip_pipe_streams)");
+    if (!ticket || ticket > s.k) return p->fail(UWIP_ERR_INVALID, "no such ticket");
+    const int slot = (int)((ticket - 1) % (uint64_t)s.sc.depth), F = p->cfg.frames;
+    if (s.ticket[slot] != ticket) return p->fail(UWIP_ERR_INVALID, "this result has been collected already");
+    const int32_t *par = s.h_par[slot].data();
+    if (s.h_par[slot].empty()) {
+        if (int rc_e = uwip_enter(p->ctx)) return p->from_ctx(rc_e);
+        const int rc = uwip_copier_wait(p->copier, s.t_table[slot]);
+        if (rc) return copier_rc(p, rc);
+        par = (const int32_t *)(s.h_table[slot] + uwip_ps::par_offset(F));
+    }
+    for (int f = 0; f < F; ++f) { h_bs[f] = par[2 * f]; h_cl[f] = par[2 * f + 1]; }
     return UWIP_OK;
 }

@@ -36,9 +36,11 @@ struct PGeo {
 // per chunk, from k_png_deflate
 struct ChunkOut { uint32_t size, crc, a, b; };
 
-__global__ __launch_bounds__(256) void k_png_filter(const uint8_t *__restrict__ img, PGeo g, int filter, uint8_t *__restrict__ filt)
+__global__ __launch_bounds__(256) void k_png_filter(const uint8_t *__restrict__ img, PGeo g, int filter, uint8_t *__restrict__ filt,
+                                                    const int32_t *__restrict__ nsel = nullptr)
 {
     __shared__ uint32_t s_scan[8];
+    if (nsel && (int)blockIdx.y >= *nsel) return;                // uniform over the workgroup, ahead of every barrier
     const int y = blockIdx.x, f = blockIdx.y, nc = g.nc, rb = g.cols * g.nc;
     const uint8_t *row = img + (size_t)f * g.fs + (size_t)y * g.step, *up = y ? row - g.step : nullptr;
     auto sample = [&](const uint8_t *r, int i) -> int {        // byte i of the row as the file has it (RGB)
@@ -86,8 +88,9 @@ __device__ __forceinline__ void walk_tokens(const uint8_t *__restrict__ d, int n
 }
 
 __global__ __launch_bounds__(256) void k_png_deflate(const uint8_t *__restrict__ filt, PGeo g, uint8_t *__restrict__ stage,
-                                                     ChunkOut *__restrict__ cout)
+                                                     ChunkOut *__restrict__ cout, const int32_t *__restrict__ nsel = nullptr)
 {
+    if (nsel && (int)blockIdx.y >= *nsel) return;
     __shared__ uint32_t s_freq[kNumLL], s_win[kWinWords], s_crc[256], s_tab[256], s_scan[8], s_nmatch;
     __shared__ int s_ls[256], s_fs[256];
     __shared__ Codes s_codes;
@@ -192,10 +195,12 @@ __global__ __launch_bounds__(256) void k_png_deflate(const uint8_t *__restrict__
 
 // per frame: where each IDAT starts behind signature and IHDR, the stream length, the Adler-32
 __global__ __launch_bounds__(256) void k_png_finish(const ChunkOut *__restrict__ cout, PGeo g, uint64_t *__restrict__ coff,
-                                                    int64_t *__restrict__ needed, uint32_t *__restrict__ adler)
+                                                    int64_t *__restrict__ needed, uint32_t *__restrict__ adler,
+                                                    const int32_t *__restrict__ nsel = nullptr)
 {
     __shared__ uint32_t s_scan[8], s_tot[2];
     const int f = blockIdx.x, t = threadIdx.x;
+    if (nsel && f >= *nsel) return;
     uint64_t off = 0;
     uint32_t A = 1, myb = 0;                                  // A: the Adler A in front of this tile
     for (int cb = 0; cb < g.nch; cb += 256) {
@@ -225,10 +230,15 @@ __global__ __launch_bounds__(256) void k_png_finish(const ChunkOut *__restrict__
 __global__ __launch_bounds__(256) void k_png_assemble(const uint8_t *__restrict__ stage, const ChunkOut *__restrict__ cout,
                                                       const uint64_t *__restrict__ coff, PGeo g, const uint8_t *__restrict__ head,
                                                       const int64_t *__restrict__ needed, const uint32_t *__restrict__ adler,
-                                                      uint8_t *__restrict__ streams, size_t slot_bytes, int64_t *__restrict__ sizes)
+                                                      uint8_t *__restrict__ streams, size_t slot_bytes, int64_t *__restrict__ sizes,
+                                                      const int32_t *__restrict__ nsel = nullptr)
 {
     __shared__ uint8_t s_tail[kTailBytes];
     const int c = blockIdx.x, f = blockIdx.y, t = threadIdx.x;
+    if (nsel && f >= *nsel) {                                   // not selected: size 0, nothing written
+        if (c == 0 && t == 0) sizes[f] = 0;
+        return;
+    }
     const int64_t need = needed[f];
     const bool fits = (uint64_t)need <= (uint64_t)slot_bytes;
     if (c == 0 && t == 0) sizes[f] = fits ? need : -need;
@@ -267,6 +277,12 @@ UWIP_API int uwip_png_chunk_bytes(void) { return kChunk; }
 
 UWIP_API int uwip_png_encode(uwip_ctx *ctx, const uwip_batch_u8 *frames, int filter, uint8_t *d_streams, size_t slot_bytes,
                              int64_t *d_sizes)
+{
+    return uwip_png_encode_dev(ctx, frames, filter, d_streams, slot_bytes, d_sizes, nullptr);
+}
+
+int uwip_png_encode_dev(uwip_ctx *ctx, const uwip_batch_u8 *frames, int filter, uint8_t *d_streams, size_t slot_bytes,
+                        int64_t *d_sizes, const int32_t *d_count)
 {
     if (!ctx) {                                               // no context: because there is no device, or a plain bad argument
         int ndev = 0;
@@ -313,20 +329,20 @@ UWIP_API int uwip_png_encode(uwip_ctx *ctx, const uwip_batch_u8 *frames, int fil
     const uint8_t *img = static_cast<const uint8_t *>(frames->data);
     {
         uwip_kscope ks(ctx, "k_png_filter");
-        k_png_filter<<<dim3(g.rows, F), 256, 0, ctx->stream>>>(img, g, filter, filt);
+        k_png_filter<<<dim3(g.rows, F), 256, 0, ctx->stream>>>(img, g, filter, filt, d_count);
     }
     {
         uwip_kscope ks(ctx, "k_png_deflate");
-        k_png_deflate<<<dim3(g.nch, F), 256, 0, ctx->stream>>>(filt, g, stage, cout);
+        k_png_deflate<<<dim3(g.nch, F), 256, 0, ctx->stream>>>(filt, g, stage, cout, d_count);
     }
     {
         uwip_kscope ks(ctx, "k_png_finish");
-        k_png_finish<<<F, 256, 0, ctx->stream>>>(cout, g, coff, needed, adler);
+        k_png_finish<<<F, 256, 0, ctx->stream>>>(cout, g, coff, needed, adler, d_count);
     }
     {
         uwip_kscope ks(ctx, "k_png_assemble");
         k_png_assemble<<<dim3(g.nch, F), 256, 0, ctx->stream>>>(stage, cout, coff, g, static_cast<const uint8_t *>(d_head), needed, adler,
-                                                                d_streams, slot_bytes, d_sizes);
+                                                                d_streams, slot_bytes, d_sizes, d_count);
     }
     UWIP_HIP(ctx, hipGetLastError());
     return UWIP_OK;

@@ -146,7 +146,20 @@ int uwip_features_copy_dev(uwip_ctx *ctx, uwip_features *f, const int32_t *d_src
 // kf_chain.hip: one walker call of the key-frame chain (kf_chain.hpp) on the device
 int uwip_kf_walk(uwip_ctx *ctx, const uwip_kf::Batch &b, uwip_kf::State *d_state, const uwip_kf::Bufs &u, int round);
 
-#define UWIP_HIP(ctx, expr)                                                          \
+// jpeg_encode.hip / png_encode.hip: uwip_jpeg_encode / uwip_png_encode with a frame count the device wrote.  d_count (null:
+// all frames) is read by every kernel: a frame at or beyond it returns at once and reports size 0.
+int uwip_jpeg_encode_dev(uwip_ctx *ctx, const uwip_batch_u8 *frames, int quality, uint8_t *d_streams, size_t slot_bytes,
+                         int64_t *d_sizes, const int32_t *d_count);
+int uwip_png_encode_dev(uwip_ctx *ctx, const uwip_batch_u8 *frames, int filter, uint8_t *d_streams, size_t slot_bytes,
+                        int64_t *d_sizes, const int32_t *d_count);
+// pipe_streams.hip: the kernels of uwip_pipe_step_streams between decoders, stages and encoders (pipe_streams.hpp)
+namespace uwip_ps { struct Step; }
+int uwip_ps_blank(uwip_ctx *ctx, uint8_t *d_frames, int F, size_t frame_bytes, const int32_t *d_status);
+int uwip_ps_select_gather(uwip_ctx *ctx, const uwip_ps::Step &s);
+int uwip_ps_pack(uwip_ctx *ctx, const uwip_ps::Step &s, const int64_t *d_sizes, const float *d_ratio, const int32_t *d_par,
+                 const uint8_t *d_slots, size_t slot_bytes, uint8_t *d_table, uint8_t *d_blob);
+
+#define UWIP_HIP(ctx, expr)                                                         \
     do {                                                                             \
         hipError_t e__ = (expr);                                                     \
         if (e__ != hipSuccess) return (ctx)->fail(UWIP_ERR_HIP, #expr, hipGetErrorString(e__)); \

@@ -22,13 +22,15 @@ import ctypes as C
 
 import torch
 
-from ._native import (KF_BLUR_FN, KF_OVERLAP_FN, Context, Copier, KeyframeConfig, KeyframeRow, PipeConfig, UwipError, batch_of,
-                      lib)
+from ._native import (KF_BLUR_FN, KF_OVERLAP_FN, Context, Copier, KeyframeConfig, KeyframeRow, PipeConfig, PipeStreamsConfig,
+                      StreamOut, UwipError, batch_of, lib)
 
 DEHAZE_FULL, DEHAZE_GUARD_S = 1, 2              # uwip.h
 OVERLAP_MIN6 = 8
 ACLAHE_PREFILTER, ACLAHE_ASYNC = 1, 4
 PIPE_DEHAZE, PIPE_HISTRETCH, PIPE_ACLAHE, PIPE_OVERLAP, PIPE_ALL = 1, 2, 4, 8, 15
+STREAM_JPEG, STREAM_PNG = 0, 1
+EMIT_ALL, EMIT_KEYFRAMES = 0, 1
 
 
 def keyframe_config(minOverlap=None, kWindow=None, lookback=None, max_rows=None) -> KeyframeConfig:
@@ -151,6 +153,73 @@ class FramePipe:
             out += [_row(buf[i]) for i in range(n.value)]
             if n.value < cap:
                 return out
+
+    # ---- compressed frames in, compressed (key) frames out (uwip_pipe_streams) -------------------------------
+    def streams(self, format: str = "jpeg", quality: int = 95, png_filter: int = -1, emit: str = "all", slot_bytes: int = 0,
+                depth: int = 2):
+        """Configure ``run_streams`` / ``collect``: the format of the emitted streams ("jpeg" / "png"), which frames are
+        emitted ("all", or "keyframes" on a pipe made with ``keyframes=``), the slot per emitted frame (0 = the raw frame
+        size) and how many steps' results stay collectable.  Before the first step or right after a reset."""
+        sc = PipeStreamsConfig()
+        self._l.uwip_pipe_streams_config_default(C.byref(sc))
+        sc.format = {"jpeg": STREAM_JPEG, "png": STREAM_PNG}[format]
+        sc.emit = {"all": EMIT_ALL, "keyframes": EMIT_KEYFRAMES}[emit]
+        sc.quality, sc.png_filter, sc.slot_bytes, sc.depth = int(quality), int(png_filter), int(slot_bytes), int(depth)
+        self._call("uwip_pipe_streams", C.byref(sc))
+        self._slot_bytes = int(slot_bytes) if slot_bytes else self.H * self.W * 3
+
+    def run_streams(self, streams) -> int:
+        """One step on `frames` compressed frames (bytes objects, .jpg and .png mixed as they come): returns the ticket of
+        the step's result without waiting for the device (uwip_pipe_step_streams)."""
+        n = len(streams)
+        bufs = [(C.c_uint8 * max(1, len(b))).from_buffer_copy(bytes(b) if len(b) else b"\0") for b in streams]
+        ptrs = (C.c_void_p * n)(*[C.addressof(b) for b in bufs])
+        sizes = (C.c_size_t * n)(*[len(b) for b in streams])
+        t = C.c_uint64(0)
+        self._call("uwip_pipe_step_streams", ptrs, sizes, n, C.byref(t))
+        self._overlap_ran()
+        self._params = None
+        return t.value
+
+    def result_params(self, ticket: int):
+        """[(BS, CL)] the aclahe stage chose in the step `ticket` names; waits for that step only, and must come before its
+        ``collect`` (uwip_pipe_result_params)."""
+        bs, cl = (C.c_int32 * self.F)(), (C.c_int32 * self.F)()
+        self._call("uwip_pipe_result_params", C.c_uint64(ticket), bs, cl)
+        return list(zip(bs, cl))
+
+    def collect(self, ticket: int, blob_cap: "int | None" = None):
+        """Wait for the step `ticket` names and return (status [frames], ratio [frames], [(index, row_id, bytes | -needed)]):
+        the decoders' statuses, the step's ratios and the emitted streams (uwip_pipe_collect)."""
+        import numpy as np
+
+        F = self.F
+        status = (C.c_int32 * F)()
+        ratio = (C.c_float * F)()
+        outs = (StreamOut * (F + 1))()
+        n = C.c_int(0)
+        need = C.c_size_t(0)
+        args = (self._p, C.c_uint64(ticket), status, ratio, outs, F + 1, C.byref(n))
+        blob, cap = None, 0
+        if blob_cap is None:
+            # ask for the size first: a call whose blob is too small fails, says how many bytes there are and keeps the result
+            rc = self._l.uwip_pipe_collect(*args, None, 0, C.byref(need))
+            if rc == 0:
+                return np.array(status, dtype=np.int32), np.array(ratio, dtype=np.float32), \
+                    [(outs[i].index, outs[i].row_id, b"" if outs[i].size >= 0 else int(outs[i].size)) for i in range(n.value)]
+            cap = need.value
+            if cap == 0:
+                raise UwipError(rc, self._l.uwip_pipe_last_error(self._p).decode("utf-8", "replace"))
+        else:
+            cap = int(blob_cap)
+        blob = (C.c_uint8 * max(1, cap))()
+        self._call("uwip_pipe_collect", *args[1:], blob, cap, C.byref(need))
+        raw = bytes(memoryview(blob)[:need.value])
+        res = []
+        for i in range(n.value):
+            o = outs[i]
+            res.append((o.index, o.row_id, raw[o.offset:o.offset + o.size] if o.size >= 0 else int(o.size)))
+        return np.array(status, dtype=np.int32), np.array(ratio, dtype=np.float32), res
 
     def _call(self, name, *args):
         rc = getattr(self._l, name)(self._p, *args)
