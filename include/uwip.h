@@ -641,12 +641,16 @@ int uwip_png_encode_host(uwip_ctx *ctx, const uwip_batch_u8 *frames, int filter,
 /* ---- reading the frames: baseline JPEG on the device ---------------------------------------------------------------
  * cv::imread / cv::imdecode for a batch, on the device (jpeg::decode of cli/jpeg.hpp is the host form; where the status is 0,
  * the same pixels byte for byte, the host decoder's rules for a truncated segment included: bits past the end, or past a
- * marker that is no RSTn, read as zeros).  Baseline (SOF0 / SOF1, 8 bit, Huffman), one interleaved scan, 1 or 3 components,
- * sampling factors 1..2, restart intervals; Motion-JPEG frames without DHT use the Annex K tables.
+ * marker that is no RSTn, read as zeros).  Baseline (SOF0 / SOF1, 8 bit, Huffman), one scan of all components, 1 or 3
+ * components, restart intervals; Motion-JPEG frames without DHT use the Annex K tables.  Three components are interleaved,
+ * have sampling factors 1..2 and at most 10 blocks per MCU (T.81 B.2.3: all three sampled 2x2 is refused).  One component
+ * is not interleaved (T.81 A.2.2): its MCU is one block, in raster order over ceil(cols / 8) x ceil(rows / 8) blocks, and
+ * the factors its SOF gives, any of 1..4, are read as 1x1, as libjpeg does; such a stream is never HOST_ONLY for its factors.
  * uwip_jpeg_info: the header parse alone (host, pure, no device needed): rows, cols and the component count (1 or 3) of a
  *   stream jpeg::decode would start to decode; UWIP_ERR_UNSUPPORTED where its parse fails (not 8 bit, progressive and the
- *   other non-baseline SOFs, more than one SOF, a component count other than 1 or 3, sampling factors outside 1..2, short
- *   segments, no scan).
+ *   other non-baseline SOFs, more than one SOF, a component count other than 1 or 3, three components with sampling factors
+ *   outside 1..2 or more than 10 blocks per MCU, short segments, no scan).  The factors of a single component do not
+ *   matter: any that SOF can hold, 1..4, are read.
  * uwip_jpeg_decode: parses the n streams on the host, copies their entropy-coded segments through page-locked staging owned
  *   by the library to the device on the context's stream, queues the kernels and returns without waiting (reuse of the
  *   staging buffer waits, polling an event, for the previous call's upload only).  `out` is a device batch of n frames with 3
@@ -657,9 +661,9 @@ int uwip_png_encode_host(uwip_ctx *ctx, const uwip_batch_u8 *frames, int filter,
  *     UWIP_JPEG_BAD_STREAM     jpeg::decode returns false: parse errors, an undecodable Huffman code, a DC category above 11,
  *                              a DC predictor outside 16 bits, a run past coefficient 63
  *     UWIP_JPEG_SIZE_MISMATCH  the SOF size is not out->rows x out->cols, or a colour stream goes into a 1-channel batch
- *     UWIP_JPEG_HOST_ONLY      the host decoder reads the stream, the device does not: a component sampled 1x2 against the
- *                              largest factors, or an entropy-coded segment whose markers before the first non-RST marker
- *                              are not exactly ceil(MCUs / Ri) - 1 RSTn in cyclic order
+ *     UWIP_JPEG_HOST_ONLY      the host decoder reads the stream, the device does not: one of three components sampled 1x2
+ *                              against the largest factors, or an entropy-coded segment whose markers before the first
+ *                              non-RST marker are not exactly ceil(MCUs / Ri) - 1 RSTn in cyclic order
  *   opts (NULL: the defaults): sync_rounds is the number of synchronisation rounds of the entropy decoder, -1 the
  *   library's choice, 0 none (one lane per restart interval decodes serially); d_unsettled, when not NULL, receives two
  *   64-bit counts on the device: subsequences still unsettled after the rounds, subsequences in all.

@@ -4,7 +4,7 @@
 // logic (and, under the sanitizers, every index they form) where there is no device; the GPU tests check the compiled kernels.
 // tests/test_jpeg_decode_emulated.py cuts the kernels out of the .hip file into kernels_dec.inc (everything inside its
 // anonymous namespace), builds this file with the host compiler and gives it the streams:
-//   emu <list file>      one line per case: <path> <sync_rounds> <channels of the batch>
+//   emu <list file>      one line per case: <path> <sync_rounds> <channels of the batch> [<file for the host decoder's pixels>]
 // and prints per case: <path> <sync_rounds> status <s> host <0|1> equal <0|1> clean <0|1> unsettled <u> of <n>
 #include <cstdio>
 #include <cstring>
@@ -63,13 +63,15 @@ int main(int argc, char **argv)
     std::string line;
     while (std::getline(list, line)) {
         std::istringstream is(line);
-        std::string path; int rounds = -1, channels = 3;
+        std::string path, dump; int rounds = -1, channels = 3;
         if (!(is >> path >> rounds >> channels)) continue;
+        is >> dump;
         std::ifstream f(path, std::ios::binary);
         std::vector<uint8_t> s((std::istreambuf_iterator<char>(f)), std::istreambuf_iterator<char>());
         int rows = 0, cols = 0, ch = 0;
         std::vector<uint8_t> host;
         const bool host_ok = jpeg::decode(s.data(), s.size(), rows, cols, ch, host, channels == 3);
+        if (host_ok && !dump.empty()) std::ofstream(dump, std::ios::binary).write((const char *)host.data(), (std::streamsize)host.size());
         int32_t ir = 0, ic = 0, ich = 0;
         const int info = uwip_jpeg::parse(s.data(), s.size(), &ir, &ic, &ich, nullptr, nullptr);
         if (!host_ok) { rows = info == 0 ? ir : 8; cols = info == 0 ? ic : 8; }

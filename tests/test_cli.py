@@ -98,6 +98,22 @@ def test_jpeg_codec_against_pillow(tmp_path):
     assert subprocess.run([conv, a, j, "grey"], capture_output=True, timeout=120).returncode == 0
     im = Image.open(j)
     assert im.mode == "L" and np.abs(np.asarray(im).astype(int) - g.astype(int)).mean() < 2.0
+    # a grey stream whose SOF keeps the 2x2 factors of a colour mode: one block per MCU all the same (T.81 A.2.2), libjpeg's
+    # pixels; and Pillow's own grey stream with that one byte of SOF rewritten
+    import _jpeg_forge_cases as fc
+    forged = dict(fc.equality_grey(37, 53))["g22_37x53_ri0"].stream
+    buf = io.BytesIO()
+    Image.fromarray(np.ascontiguousarray(g[:53, :37])).save(buf, format="JPEG", quality=90)
+    own = buf.getvalue()
+    sof = own.index(b"\xff\xc0")
+    assert own[sof + 9] == 1 and own[sof + 11] == 0x11
+    patched = own[:sof + 11] + b"\x22" + own[sof + 12:]
+    for name, s in (("forged", forged), ("patched", patched)):
+        open(j, "wb").write(s)
+        r = subprocess.run([conv, j, out], capture_output=True, text=True, timeout=120)
+        assert r.returncode == 0, (name, r.stdout)
+        assert np.array_equal(_load_png(out), np.asarray(Image.open(io.BytesIO(s)).convert("RGB"))[..., ::-1]), name
+    assert np.array_equal(np.asarray(Image.open(io.BytesIO(patched))), np.asarray(Image.open(io.BytesIO(own))))
 
 
 def test_jpeg_header_is_the_one_pillow_writes(tmp_path):

@@ -7,6 +7,7 @@ import re
 import numpy as np
 import pytest
 
+import _jpeg_forge_cases as fc
 import _jpeg_streams as js
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -48,6 +49,39 @@ def test_info_rejections():
                 good[:sof + 4] + b"\x0c" + good[sof + 5:]):                     # 12-bit precision
         with pytest.raises(uw.UwipError):
             uw.jpeg.info(bad)
+
+
+def test_info_of_forged_geometries():
+    """An MCU of more than 10 blocks is no baseline stream (T.81 B.2.3): UWIP_ERR_UNSUPPORTED.  The SOF factors of a single
+    component do not matter; every other triple of factors 1..2 parses."""
+    import uwimageproc_amd as uw
+    import uwimageproc_amd._native as nat
+    s = fc.twelve_blocks().stream
+    buf = (C.c_uint8 * len(s)).from_buffer_copy(s)
+    r, c, ch = C.c_int32(5), C.c_int32(5), C.c_int32(5)
+    assert nat.lib().uwip_jpeg_info(C.cast(buf, C.c_void_p), len(s), C.byref(r), C.byref(c), C.byref(ch)) == nat.UWIP_ERR_UNSUPPORTED
+    with pytest.raises(uw.UwipError):
+        uw.jpeg.info(s)
+    for W, H in fc.SIZES:
+        for n, f in fc.equality_grey(W, H):
+            assert uw.jpeg.info(f.stream) == (H, W, 1), n
+        for n, f in fc.equality_colour(W, H):
+            assert uw.jpeg.info(f.stream) == (H, W, 3), n
+    for n, f in fc.header_streams() + fc.restart_streams():
+        assert uw.jpeg.info(f.stream) == (53, 37, 3), n
+    # one component: any factors that SOF can hold, 1..4, and no others (libjpeg refuses those too)
+    g = fc.equality_grey_to_4()[0][1].stream
+    at = g.index(b"\xff\xc0") + 11
+    assert g[at] == 0x43 and uw.jpeg.info(g) == (53, 37, 1)
+    for n, f in fc.equality_grey_to_4():
+        assert uw.jpeg.info(f.stream) == (53, 37, 1), n
+    for byte in (0x44, 0x14, 0x41):
+        assert uw.jpeg.info(g[:at] + bytes([byte]) + g[at + 1:]) == (53, 37, 1), hex(byte)
+    for byte in (0x51, 0x15, 0x01, 0x10, 0x00, 0xF1):
+        with pytest.raises(uw.UwipError):
+            uw.jpeg.info(g[:at] + bytes([byte]) + g[at + 1:])
+        with pytest.raises(Exception):
+            js.pil_decode(g[:at] + bytes([byte]) + g[at + 1:], 1)
 
 
 def test_null_arguments_and_no_device():

@@ -7,6 +7,7 @@ import subprocess
 import numpy as np
 import pytest
 
+import _jpeg_forge_cases as fc
 import _jpeg_streams as js
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -25,13 +26,16 @@ def emu(tmp_path_factory):
                     "-I", os.path.join(ROOT, "uwimageproc_amd", "csrc"), os.path.join(ROOT, "tests", "jpeg_decode_emulated.cpp"),
                     "-o", exe], check=True, timeout=600)
 
-    def run(cases):
-        """cases: [(name, stream, channels, rounds)] -> {(name, rounds): dict of the printed fields}"""
+    def run(cases, dump=False):
+        """cases: [(name, stream, channels, rounds)] -> {(name, rounds): dict of the printed fields}; with `dump` also
+        "pixels": the bytes the host decoder returned (None where it refused)"""
         lines = []
         for name, stream, ch, rounds in cases:
             p = str(d / (name + ".jpg"))
             open(p, "wb").write(stream)
-            lines.append(f"{p} {rounds} {ch}")
+            if dump and os.path.exists(p[:-4] + ".host"):
+                os.remove(p[:-4] + ".host")
+            lines.append(f"{p} {rounds} {ch}" + (f" {p[:-4]}.host" if dump else ""))
         lst = str(d / "list.txt")
         open(lst, "w").write("\n".join(lines) + "\n")
         r = subprocess.run([exe, lst], capture_output=True, text=True, timeout=1500)
@@ -42,6 +46,9 @@ def emu(tmp_path_factory):
             out[(os.path.basename(w[0])[:-4], int(w[1]))] = {"status": int(w[3]), "host": int(w[5]), "equal": int(w[7]), "clean": int(w[9]),
                                                             "unsettled": int(w[11]), "lanes": int(w[13])}
         assert len(out) == len(cases), r.stdout[-3000:]
+        for (name, _), v in out.items() if dump else ():
+            p = str(d / (name + ".host"))
+            v["pixels"] = open(p, "rb").read() if os.path.exists(p) else None
         return out
     return run
 
@@ -184,3 +191,121 @@ def test_mutated_headers_are_accepted_or_rejected_as_the_host_decoder_does(emu):
         else:
             assert v["status"] in (-2, -3) and v["host"], (name, v)      # a size the batch does not have / host only: both decodable
     assert n_bad > 20
+
+
+# ---- streams no libjpeg encoder writes (tests/_jpeg_forge.py), against Pillow's decode ------------------------------------------
+ROUNDS = (0, 1, -1)
+
+
+def _equal_pillow(emu, named, channels=3):
+    """Emulated kernels == host decoder == Pillow, status 0, at every round count."""
+    tag = "" if channels == 3 else "_ch1"
+    res = emu([(n + tag, f.stream, channels, r) for n, f in named for r in ROUNDS], dump=True)
+    for n, f in named:
+        want = js.pil_decode(f.stream, channels)
+        for r in ROUNDS:
+            v = res[(n + tag, r)]
+            assert v["status"] == 0 and v["host"] and v["equal"] and v["clean"], (n, r, {k: x for k, x in v.items() if k != "pixels"})
+        host = np.frombuffer(res[(n + tag, -1)]["pixels"], dtype=np.uint8).reshape(want.shape)
+        assert np.array_equal(host, want), (n, int(np.abs(host.astype(int) - want).max()), float((host != want).mean()))
+    return res
+
+
+def test_forged_factor_combinations_equal_pillow(emu):
+    """The factors are enumerated from the rule of include/uwip.h: 64 triples of (h, v) in 1..2; a component with hmax / h == 1
+    and vmax / v == 2 is HOST_ONLY.  hmax = vmax = 2 needs a 2x2 component and allows 2x2, 1x1 and 1x2 beside it: 27 - 8 = 19.
+    hmax = 2, vmax = 1: 2x1 and 1x1 with at least one 2x1: 7.  hmax = 1, vmax = 2: all 1x2 (a 1x1 would be 1x2 against it).
+    All 1x1.  28, less the triple of 2x2 with its 12 blocks: 27."""
+    assert len(fc.device_eligible()) == 27 and [(2, 2)] * 3 not in fc.device_eligible()
+    for W, H in fc.SIZES:
+        named = fc.equality_colour(W, H)
+        assert len(named) == 54
+        _equal_pillow(emu, named)
+
+
+def test_forged_grey_is_one_block_per_mcu_whatever_sof_says(emu):
+    for W, H in fc.SIZES:
+        named = fc.equality_grey(W, H)
+        assert len(named) == 12
+        for h, v in fc.GREY_FACTORS[1:]:                # the same bytes but for the factors in SOF
+            a, b = dict(named)[f"g11_{W}x{H}_ri5"].stream, dict(named)[f"g{h}{v}_{W}x{H}_ri5"].stream
+            assert [i for i in range(len(a)) if a[i] != b[i]] == [a.index(b"\xff\xc0") + 11] and len(a) == len(b)
+        _equal_pillow(emu, named)
+        _equal_pillow(emu, named, channels=1)
+    # factors of 3 and 4, which SOF can hold and no three-component stream may have here
+    named = fc.equality_grey_to_4()
+    assert len(named) == 6
+    _equal_pillow(emu, named)
+    _equal_pillow(emu, named, channels=1)
+
+
+def test_forged_mcu_of_twelve_blocks_is_refused(emu):
+    """T.81 B.2.3: an MCU has at most 10 blocks; libjpeg refuses the stream, and so do both decoders."""
+    f = fc.twelve_blocks()
+    assert f.bpm == 12
+    with pytest.raises(Exception):
+        js.pil_decode(f.stream)
+    res = emu([("twelve", f.stream, 3, r) for r in ROUNDS])
+    for r in ROUNDS:
+        v = res[("twelve", r)]
+        assert v["status"] == -1 and not v["host"] and v["clean"], (r, v)
+
+
+def test_forged_restart_intervals_equal_pillow(emu):
+    named = fc.restart_streams()
+    assert len(named) == 18
+    for tag in ("420", "422", "444"):
+        f = dict(named)[f"r{tag}_ri1"]
+        seg = f.stream[f.seg:]
+        assert f.nmcu > 9 and seg.count(b"\xff\xd0") >= 2 and b"\xff\xd7" in seg                  # RSTn wraps
+        assert f.rst_after_stuffed > 0 and any(b"\xff\x00\xff" + bytes([0xD0 + i]) in seg for i in range(8))
+        for ri in (f.nmcu, f.nmcu + 1, 65535):             # an interval that holds every MCU: DRI, and no RSTn
+            g = dict(named)[f"r{tag}_ri{ri}"]
+            assert b"\xff\xdd" in g.stream[:g.seg] and not any(bytes([0xFF, 0xD0 + i]) in g.stream[g.seg:] for i in range(8))
+    _equal_pillow(emu, named)
+
+
+def test_forged_long_stream_settles_over_the_rounds(emu):
+    """One interval of many subsequences: lanes that start in the middle of it read codes that are none, runs past 63 and
+    categories above 11 where no symbol starts.  What such a start reads must never become the frame's status."""
+    f = fc.long_stream()
+    res = _equal_pillow(emu, [("long", f)])
+    assert res[("long", -1)]["lanes"] > 100
+    assert res[("long", 0)]["unsettled"] > 0 and res[("long", 0)]["status"] == 0 and res[("long", 0)]["equal"]
+    assert res[("long", 0)]["unsettled"] > res[("long", 1)]["unsettled"] >= res[("long", -1)]["unsettled"]
+
+
+def test_forged_header_forms_equal_pillow(emu):
+    named = fc.header_streams()
+    assert [n for n, _ in named] == ["h_q16", "h_dht23", "h_fill", "h_sof1", "h_ids", "h_com", "h_dri0", "h_all"]
+    f = dict(named)["h_all"]
+    head = f.stream[:f.seg]
+    assert head.index(b"\xff\xda") < f.seg - 14 and b"\xff\xff\xff\xc1" in head and head.count(b"\xff\xdd") == 2 and head.count(b"\xff\xc4") == 1
+    _equal_pillow(emu, named)
+
+
+def test_forged_faults_are_bad_stream_and_their_twins_decode(emu):
+    """include/uwip.h, UWIP_JPEG_BAD_STREAM: a DC category above 11, a run past coefficient 63, an undecodable code, a DC
+    predictor outside 16 bits.  Each at the first block, behind four subsequences, at the last block and inside a later
+    restart interval; the twin is the same stream one step inside the rule (category 11, a run to 63, the longest code,
+    a predictor of 32752) and decodes."""
+    cases = fc.bad_streams()
+    assert len(cases) == 16
+    lines = []
+    for name, bad, twin, inside, at in cases:
+        if name.endswith("_deep"):
+            assert bad.pos[at][0] == 0 and bad.pos[at][1] >= 4 * fc.SUB_BITS and twin.pos[at][1] >= 4 * fc.SUB_BITS
+        if name.endswith("_last"):
+            assert at == len(bad.coefs) - 1
+        if name.endswith("_iv5"):
+            assert bad.pos[at][0] == 5 and twin.pos[at][0] == 5
+        lines += [(name, bad.stream, 3, r) for r in ROUNDS] + [(name + "_twin", twin.stream, 3, r) for r in ROUNDS]
+    res = emu(lines, dump=True)
+    for name, bad, twin, inside, at in cases:
+        for r in ROUNDS:
+            v, t = res[(name, r)], res[(name + "_twin", r)]
+            assert v["status"] == -1 and not v["host"] and v["clean"], (name, r, v["status"], v["host"], v["clean"])
+            assert t["status"] == 0 and t["host"] and t["equal"] and t["clean"], (name, r, t["status"], t["host"], t["equal"], t["clean"])
+        if inside:
+            want = js.pil_decode(twin.stream)
+            assert np.array_equal(np.frombuffer(res[(name + "_twin", -1)]["pixels"], dtype=np.uint8).reshape(want.shape), want), name

@@ -96,10 +96,11 @@ inline void std_spec(HuffSpec &t, const uint8_t *bits, const uint8_t *vals, int 
 enum { PARSE_OK = 0, PARSE_BAD = -1, PARSE_HOST_ONLY = -3 };       // the values of UWIP_JPEG_BAD_STREAM / _HOST_ONLY
 
 // The walk from SOI to the end of SOS.  PARSE_BAD: not the baseline both decoders read (SOF0 / SOF1, 8 bit, 1 or 3 components
-// with sampling factors 1 or 2, one interleaved scan), a malformed segment, a table the scan names but no DHT or default
-// gives, or no scan at all.  On PARSE_OK / PARSE_HOST_ONLY (1x2 sampling: the host decoder alone upsamples it) the geometry,
-// the quantisers and the tables of `d` are filled in and the entropy-coded segment is buf[*seg .. len).  `d` may be null
-// (uwip_jpeg_info: sizes only).
+// with sampling factors 1 or 2 and at most 10 blocks per MCU, one scan of all components), a malformed segment, a table the
+// scan names but no DHT or default gives, or no scan at all.  The factors of a single component, any of 1..4, are taken as
+// 1x1.  On PARSE_OK / PARSE_HOST_ONLY (1x2 sampling: the host decoder alone upsamples it) the geometry, the quantisers and
+// the tables of `d` are filled in and the entropy-coded segment is buf[*seg .. len).  `d` may be null (uwip_jpeg_info:
+// sizes only).
 inline int parse(const uint8_t *buf, size_t len, int *rows, int *cols, int *channels, DecFrame *d, size_t *seg)
 {
     if (!buf || len < 4 || buf[0] != 0xFF || buf[1] != 0xD8) return PARSE_BAD;
@@ -153,9 +154,15 @@ inline int parse(const uint8_t *buf, size_t len, int *rows, int *cols, int *chan
             for (int i = 0; i < n; ++i) {
                 comp[i].id = s[6 + 3 * i]; comp[i].h = s[7 + 3 * i] >> 4; comp[i].v = s[7 + 3 * i] & 15; comp[i].tq = s[8 + 3 * i] & 3;
                 comp[i].td = comp[i].ta = 0;
+                // a one-component scan is not interleaved (T.81 A.2.2): one block per MCU, in raster order over ceil(W / 8) x
+                // ceil(H / 8) blocks, whatever factors SOF gives the component -- any the format can write (1..4) are read
+                // as 1x1, as libjpeg does
+                if (n == 1 && comp[0].h >= 1 && comp[0].h <= 4 && comp[0].v >= 1 && comp[0].v <= 4) comp[0].h = comp[0].v = 1;
                 if (comp[i].h < 1 || comp[i].h > 2 || comp[i].v < 1 || comp[i].v > 2) return PARSE_BAD;
                 hmax = comp[i].h > hmax ? comp[i].h : hmax; vmax = comp[i].v > vmax ? comp[i].v : vmax;
             }
+            // T.81 B.2.3: at most 10 blocks in an MCU (three components all 2x2 have 12; libjpeg refuses them too)
+            if (n == 3 && comp[0].h * comp[0].v + comp[1].h * comp[1].v + comp[2].h * comp[2].v > 10) return PARSE_BAD;
             have_sof = true;
         } else if (m == 0xC2 || (m >= 0xC5 && m <= 0xCF && m != 0xC8 && m != 0xCC)) {
             return PARSE_BAD;                   // progressive / lossless / arithmetic
