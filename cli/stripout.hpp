@@ -1,0 +1,50 @@
+// --strip for the CLIs that know key frames: every exported key frame goes into a uw::Strip where the program writes it
+// (main.cpp:294,377), and at the end of the input each segment is rendered and written as <prefix>strip_NNN.<ext>, with one
+// line per segment after the report's table:  Strip:\t<file>\t<first ID>\t<count>\t<cols> x <rows>
+#pragma once
+#include <memory>
+#include <ostream>
+#include "cliutil.hpp"
+
+struct StripOut {
+    bool on = false;
+    int mode = UWIP_STRIP_FEATHER;
+    int max_frames = 1024;
+    unsigned detect_flags = 0, match_flags = 0;
+    std::shared_ptr<uw::Strip> strip;             // made at the first key frame; declare a StripOut after its context
+
+    // --strip [--strip-mode feather|first|last] [--strip-max N]; false: an unknown mode
+    bool configure(const Args &a)
+    {
+        on = a.has("strip");
+        const std::string m = a.get("strip-mode", "feather");
+        if (m == "feather") mode = UWIP_STRIP_FEATHER;
+        else if (m == "first") mode = UWIP_STRIP_FIRST;
+        else if (m == "last") mode = UWIP_STRIP_LAST;
+        else return false;
+        max_frames = std::max(1, std::atoi(a.get("strip-max", "1024").c_str()));
+        return true;
+    }
+    void add(uw::Context &ctx, imgio::Image &im)
+    {
+        if (!on) return;
+        if (!strip) strip.reset(new uw::Strip(ctx, im.rows, im.cols, max_frames, detect_flags, match_flags));
+        strip->add(as_mat(im));
+    }
+    void finish(const std::string &prefix, const char *ext, std::ostream &report)
+    {
+        if (!on || !strip) return;
+        const std::vector<uwip_strip_segment> segs = strip->layout();
+        for (size_t i = 0; i < segs.size(); ++i) {
+            uw::Mat m;
+            imgio::Image im;
+            strip->render((int)i, mode, m, im.data);
+            im.rows = m.rows; im.cols = m.cols; im.channels = 3;
+            char name[512];
+            std::snprintf(name, sizeof name, "%sstrip_%03zu.%s", prefix.c_str(), i, ext);
+            if (!imgio::imwrite(name, im)) throw uw::Error(UWIP_ERR_INVALID, std::string("cannot write ") + name);
+            std::printf("Strip: %s  key frames %d..%d  %d x %d\n", name, segs[i].first, segs[i].first + segs[i].count - 1, segs[i].cols, segs[i].rows);
+            report << "Strip:\t" << name << "\t" << segs[i].first << "\t" << segs[i].count << "\t" << segs[i].cols << " x " << segs[i].rows << "\n";
+        }
+    }
+};

@@ -11,6 +11,9 @@
 // device (uwip_pipe_keyframe_chain); <prefix>videostrip_report.txt gets its rows with the reference's columns (ID, Frame,
 // Filename, Overlap, Blur), Filename = the enhanced frame that is the key frame.  Overlap in uwpipe_report.txt is then the
 // overlap against the current key frame (nan: not compared).
+// --keyframes --strip [--strip-mode feather|first|last]: the enhanced key frames are also chained by their homographies and
+// blended into one image per segment, <prefix>strip_NNN.<ext>, with a "Strip:" line per segment after the table of
+// videostrip_report.txt (cli/stripout.hpp).  Refused with --streams, where the frames never reach the host.
 // --device-jpeg: the enhanced frames of a step are encoded on the device (uwip_jpeg_encode_host on the pipe's context, from
 // the step's frames in the staging area) and the files are written from the returned streams: the same bytes as without it.
 // --device-png: the files are .png, encoded on the device in the same way (uwip_png_encode_host): the pixels of --png, other bytes.
@@ -31,15 +34,17 @@
 #include <cstring>
 #include <fstream>
 #include "avi.hpp"
+#include "stripout.hpp"
+#include <deque>
 #include "cliutil.hpp"
 
 int main(int argc, char **argv)
 {
-    const Args a = parse_args(argc, argv, {"b", "batch", "c", "w", "window", "k", "p", "lookback"});
+    const Args a = parse_args(argc, argv, {"b", "batch", "c", "w", "window", "k", "p", "lookback", "strip-mode", "strip-max"});
     if (a.pos.size() < 2 || a.has("h") || a.has("help")) {
         std::printf("uwpipe - bgdehaze -> histretch -> aclahe -> overlap of every frame against its predecessor\n"
                     "usage: uwpipe [-b N] [-c LETTERS] [-w N] [--guard-s] [--min6] [--relative-threshold] [--png] [--device-jpeg]\n"
-                    "              [--device-png] [--device-decode] [--streams] [--keyframes [-k N] [-p X] [--lookback D]] <video.avi (Motion-JPEG) | frame_list.txt> <output_prefix>\n"
+                    "              [--device-png] [--device-decode] [--streams] [--keyframes [-k N] [-p X] [--lookback D] [--strip]] <video.avi (Motion-JPEG) | frame_list.txt> <output_prefix>\n"
                     "  -b N      frames per step (default 8)\n"
                     "  -c L      histretch letters (default RGB)\n"
                     "  -w N      bgdehaze window (default 15)\n"
@@ -51,7 +56,11 @@ int main(int argc, char **argv)
                     "  --keyframes   select key frames as videostrip does (report: <prefix>videostrip_report.txt)\n"
                     "  -k N          frames of the refinement window (default 11)\n"
                     "  -p X          minOverlap (default 0.4)\n"
-                    "  --lookback D  frames matched ahead per frame (a speed knob; the results do not depend on it)\n");
+                    "  --lookback D  frames matched ahead per frame (a speed knob; the results do not depend on it)\n"
+                    "  --strip       with --keyframes: also blend the enhanced key frames into <prefix>strip_NNN.<ext>, one image per chained\n"
+                    "                segment (--strip-mode feather|first|last; --strip-max N key frames, default 1024: the strip keeps them\n"
+                    "                at 640 wide in device memory, about 0.7 MB each, allocated at the first one; key frame N + 1 ends the\n"
+                    "                program with an error).  Not with --streams: the frames never reach the host there\n");
         return 0;
     }
     const std::string InputFile = a.pos[0], OutputFile = a.pos[1];
@@ -98,6 +107,29 @@ int main(int argc, char **argv)
         if (a.has("p")) kc.minOverlap = (float)std::atof(a.get("p", "0.4").c_str());
         if (a.has("lookback")) kc.lookback = std::atoi(a.get("lookback", "8").c_str());
         if (kf) CK(uwip_pipe_keyframe_chain(pipe, &kc), "uwip_pipe_keyframe_chain");
+        // --strip: the enhanced key frames go into a strip as their rows arrive (cli/stripout.hpp).  The rows are then read after
+        // every batch, and the enhanced frames of the last kWindow + 2 B + 2 stream positions are kept on the host: a row names a
+        // frame at most a window and a batch back
+        uw::Context strip_ctx(ctx);                        // a view: the context stays this program's
+        StripOut strip;
+        if (!strip.configure(a)) { std::printf("--strip-mode: feather, first or last\n"); rc = UWIP_ERR_INVALID; what = "--strip-mode"; goto fail; }
+        strip.detect_flags = cfg.detect_flags; strip.match_flags = cfg.match_flags;
+        if (strip.on && !kf) { std::printf("--strip needs --keyframes: the strip is made of the key frames\n"); rc = UWIP_ERR_INVALID; what = "--strip"; goto fail; }
+        if (strip.on && a.has("streams")) {
+            std::printf("--strip is refused with --streams: the enhanced frames never reach the host there; run without --streams\n");
+            rc = UWIP_ERR_UNSUPPORTED; what = "--strip"; goto fail;
+        }
+        std::deque<std::pair<size_t, std::vector<uint8_t>>> recent;
+        const size_t keep = (size_t)std::max(0, kc.kWindow) + 2 * (size_t)B + 2;
+        auto strip_add = [&](int index, const char *file) -> bool {
+            try {
+                imgio::Image im;
+                for (auto &r : recent) if (r.first == (size_t)index) { im.rows = rows; im.cols = cols; im.channels = 3; im.data = r.second; }
+                if (im.empty() && !imgio::imread(file, im, true)) { std::printf("cannot read back %s\n", file); return false; }
+                strip.add(strip_ctx, im);
+                return true;
+            } catch (const uw::Error &e) { std::printf("error: strip: %s\n", e.what()); return false; }
+        };
         std::ofstream kreport;
         std::vector<uwip_keyframe_row> krows(256);
         const size_t kread = (size_t)std::max(1, kc.max_rows / (2 * (B + 1)));
@@ -328,12 +360,17 @@ int main(int argc, char **argv)
                     out.data.assign((uint8_t *)h_out + fbytes * j, (uint8_t *)h_out + fbytes * (j + 1));
                 }
                 if (!written && !imgio::imwrite(name, out)) { std::printf("cannot write %s\n", name); rc = UWIP_ERR_INVALID; what = "writing"; goto fail; }
+                if (strip.on) {
+                    if (!have_out) { CK(uwip_memcpy_d2h(ctx, h_out, d_out, fbytes * B), "uwip_memcpy_d2h"); have_out = true; }
+                    recent.emplace_back(i, std::vector<uint8_t>((uint8_t *)h_out + fbytes * j, (uint8_t *)h_out + fbytes * (j + 1)));
+                    while (recent.size() > keep) recent.pop_front();
+                }
                 // frame 0 is its own key frame (main.cpp:284-297): its row carries the self-overlap
                 report << i << "\t" << name << "\t" << ((float *)h_ratio)[j] << "\t" << bs[j] << "\t" << cl[j] << "\n";
             }
             // the rows are read every `kread` batches and after the last one (each read drains the stream): at most B + 1 rows
             // close per batch, so the ring (max_rows) never holds more than half of its capacity unread
-            const bool read_rows = kf && ((k + 1) % kread == 0 || !more);
+            const bool read_rows = kf && (strip.on || (k + 1) % kread == 0 || !more);
             for (int got = (int)krows.size(); read_rows && got == (int)krows.size();) {
                 CK(uwip_pipe_keyframes(pipe, krows.data(), (int)krows.size(), &got), "uwip_pipe_keyframes");
                 for (int r = 0; r < got; ++r) {
@@ -342,12 +379,15 @@ int main(int argc, char **argv)
                     std::snprintf(name, sizeof name, "%s%04d.%s", OutputFile.c_str(), w.index, ext);
                     if (w.id == 0) kreport << "0\t0\t" << name << "\t0.0\t0.0\n";              // main.cpp:297
                     else kreport << w.id << "\t" << w.frame << "\t" << name << "\t" << w.overlap << "\t" << w.blur << "\n";   // :381
+                    if (strip.on && !strip_add(w.index, name)) { rc = UWIP_ERR_INVALID; what = "--strip"; goto fail; }
                 }
             }
             std::printf("\rbatch %zu / %zu", k + 1, nb);
             std::fflush(stdout);
         }
         std::printf("\nEnd of input.\n");
+        try { strip.finish(OutputFile, ext, kreport); }
+        catch (const uw::Error &e) { std::printf("error: strip: %s\n", e.what()); rc = UWIP_ERR_INVALID; what = "--strip"; goto fail; }
     }
 fail:
     if (rc) std::printf("error: %s: %s\n", what, pipe ? uwip_pipe_last_error(pipe) : (ctx ? uwip_last_error(ctx) : "no context"));

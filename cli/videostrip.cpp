@@ -7,11 +7,15 @@
 // PNG instead) and <prefix>videostrip_report.txt with the reference's TSV columns
 // (main.cpp:263,297,381).  The selector loop is main.cpp:300-394 as written, except that the end
 // of the input ends the program with exit code 0 (the reference calls exit(EXIT_FAILURE), B-14).
+// --strip [--strip-mode feather|first|last]: the exported key frames are also chained by their homographies and blended
+// into one image per segment, <prefix>strip_NNN.<ext>, with a "Strip:" line per segment after the report's table
+// (cli/stripout.hpp).  Without the flag the report and the files are what they were.
 #include <cmath>
 #include <fstream>
 #include <thread>
 #include "cliutil.hpp"
 #include "avi.hpp"
+#include "stripout.hpp"
 
 static const int TARGET_WIDTH = 640;          // videostrip.hpp:48
 static const double OVERLAP_MIN = 0.4;        // videostrip.hpp:50
@@ -32,15 +36,19 @@ struct FrameRec {
 
 int main(int argc, char **argv)
 {
-    const Args a = parse_args(argc, argv, {"k", "windowSize", "s", "timeSkip", "p", "minOverlap", "g", "gpus"});
+    const Args a = parse_args(argc, argv, {"k", "windowSize", "s", "timeSkip", "p", "minOverlap", "g", "gpus", "strip-mode", "strip-max"});
     if (a.pos.size() < 2 || a.has("h") || a.has("help")) {
         std::printf("videostrip - smart extraction of video frames\n"
-                    "usage: videostrip [-k windowSize] [-s timeSkip] [-p minOverlap] [-r] [--png] [--min6] [--relative-threshold] [-g gpus] <video.avi (Motion-JPEG) | frame_list.txt> <output_prefix>\n"
+                    "usage: videostrip [-k windowSize] [-s timeSkip] [-p minOverlap] [-r] [--png] [--min6] [--relative-threshold] [-g gpus] [--strip [--strip-mode feather|first|last]] <video.avi (Motion-JPEG) | frame_list.txt> <output_prefix>\n"
                     "  default: any homography found from >= 4 good matches counts, as in the reference (videostrip.cpp:252-272)\n"
                     "  --min6  a homography needs >= 6 RANSAC inliers, else -2.0 (a deviation; --min4 is accepted and names the default)\n"
                     "  default: fixed detector threshold, as SURF's hessianThreshold is fixed (videostrip.cpp:206)\n"
                     "  --relative-threshold  detector threshold relative to the frame's contrast: raw frames of turbid water have no\n"
-                    "          response above a fixed threshold (a deviation; use it together with --min6)\n");
+                    "          response above a fixed threshold (a deviation; use it together with --min6)\n"
+                    "  --strip  also blend the exported key frames into <prefix>strip_NNN.<ext>, one image per chained segment\n"
+                    "          (--strip-mode feather|first|last, default feather; --strip-max N key frames, default 1024: the strip keeps\n"
+                    "          them at 640 wide in device memory, about 0.7 MB each, allocated at the first one; key frame N + 1 ends the\n"
+                    "          program with an error)\n");
         return 0;
     }
     const int kWindow = std::atoi(a.get("k", a.get("windowSize", std::to_string(DEFAULT_KWINDOW))).c_str());
@@ -50,6 +58,9 @@ int main(int argc, char **argv)
     const char *ext = a.has("png") ? "png" : "jpg";
     const unsigned match_flags = a.has("min6") ? UWIP_OVERLAP_MIN6 : 0u;
     const unsigned detect_flags = a.has("relative-threshold") ? UWIP_OVERLAP_RELATIVE_THRESHOLD : 0u;
+    StripOut strip_cfg;                                    // the options only: the strip itself lives inside its context's scope
+    if (!strip_cfg.configure(a)) { std::printf("--strip-mode: feather, first or last\n"); return EXIT_FAILURE; }
+    strip_cfg.detect_flags = detect_flags; strip_cfg.match_flags = match_flags;
     std::vector<std::string> frames;
     avi::Reader video;
     const bool is_avi = imgio::ends_with(InputFile, ".avi");
@@ -120,6 +131,7 @@ int main(int argc, char **argv)
             // ---- the decision chain on GPU 0
             const int LOOKAHEAD = 8;
             uw::Context ctx(0);
+            StripOut strip = strip_cfg;
             uwip_features *fs = nullptr;
             ctx.check(uwip_features_create(ctx.get(), 1 + LOOKAHEAD, &fs));
             float *d_ratio = nullptr;
@@ -144,6 +156,7 @@ int main(int argc, char **argv)
             std::snprintf(name, sizeof name, "%s%04d.%s", OutputFile.c_str(), out_frame, ext);
             read_at(first, out_img);
             imgio::imwrite(name, out_img);
+            strip.add(ctx, out_img);
             report << "0\t0\t" << name << "\t0.0\t0.0\n";
             size_t key = 0, nxt = 1;
             int read_frames = 1;
@@ -181,12 +194,14 @@ int main(int argc, char **argv)
                     std::snprintf(name, sizeof name, "%s%04d.%s", OutputFile.c_str(), out_frame, ext);
                     read_at(first + key, out_img);
                     imgio::imwrite(name, out_img);
+                    strip.add(ctx, out_img);
                     std::printf("\nExported frame: %d [%d]\n", best_frame_number, out_frame);
                     report << out_frame << "\t" << best_frame_number << "\t" << name << "\t" << currOverlap << "\t" << bestBlur << "\n";
                     if (eof) break;
                 }
             }
             std::printf("\nEnd of input.\n");
+            strip.finish(OutputFile, ext, report);
             uwip_free(ctx.get(), d_ratio);
             uwip_features_destroy(fs);
         } catch (const uw::Error &e) {
@@ -198,6 +213,7 @@ int main(int argc, char **argv)
 
     try {
         uw::Context ctx(0);
+        StripOut strip = strip_cfg;
         uw::Videostrip vsx(ctx);
         vsx.match_flags = match_flags;
         vsx.detect_flags = detect_flags;
@@ -220,6 +236,7 @@ int main(int argc, char **argv)
         char name[512];
         std::snprintf(name, sizeof name, "%s%04d.%s", OutputFile.c_str(), out_frame, ext);   // :293-297
         imgio::imwrite(name, kimg);
+        strip.add(ctx, kimg);
         report << "0\t0\t" << name << "\t0.0\t0.0\n";
         for (;;) {                                                                        // :300
             if (!read_frame(frame)) { std::printf("\nEnd of input.\n"); break; }          // :303-307 (B-14)
@@ -248,12 +265,14 @@ int main(int argc, char **argv)
                 out_frame++;
                 std::snprintf(name, sizeof name, "%s%04d.%s", OutputFile.c_str(), out_frame, ext);
                 imgio::imwrite(name, kimg);
+                strip.add(ctx, kimg);
                 std::printf("\nExported frame: %d [%d]\n", best_frame_number, out_frame);
                 report << out_frame << "\t" << best_frame_number << "\t" << name << "\t" << currOverlap << "\t" << bestBlur << "\n";   // :381
                 std::printf("*************\n");
                 if (eof) { std::printf("End of input.\n"); break; }
             }
         }
+        strip.finish(OutputFile, ext, report);
         uw::Videostrip::releaseKeyframe(kframe);
     } catch (const uw::Error &e) {
         std::printf("error: %s\n", e.what());

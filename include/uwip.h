@@ -793,6 +793,64 @@ int uwip_pipe_collect(uwip_pipe *p, uint64_t ticket, int32_t *h_status, float *h
                       int *n_outs, uint8_t *h_blob, size_t blob_cap, size_t *blob_bytes);
 int uwip_pipe_result_params(uwip_pipe *p, uint64_t ticket, int32_t *h_bs, int32_t *h_cl);
 
+/* ---- strip mosaic: the key frames warped and blended into one image ------------------------------------------------
+ * The reference calls videostrip "automatic frame extraction for 2D mosaic" and stops at the frame list (main.cpp:368-381
+ * writes the key frame and its row); the homography calcOverlap computes per pair (findHomography, videostrip.cpp:270) is
+ * used for overlapArea alone (:280).  A strip continues from there: it keeps the frames it is given at the working size
+ * (cv::resize to 640 wide, main.cpp:242,311), matches every frame against its predecessor with the matcher's d_H output,
+ * chains the homographies (G_0 = I, G_k = G_{k-1} H_k, normalised), lays out one canvas per SEGMENT -- a frame that cannot be
+ * chained (no homography, a degenerate or implausible one, a canvas beyond the limit) starts a new one -- and renders a
+ * segment by a gather over the canvas: every pixel samples every frame that covers it, bilinearly with 5-bit fractions.
+ * The arithmetic is stated once in csrc/strip_core.hpp and is exact: coordinates in float64 without
+ * fused operations, everything behind the source position in integers.
+ * A quick look, not a mosaic: working resolution only, no exposure compensation, no bundle adjustment, no loop closure.
+ * A strip is bound to the context it was made from (its stream, its thread rule); destroy it before the context. */
+typedef struct uwip_strip uwip_strip;
+typedef struct uwip_strip_config {
+    int32_t  rows, cols;                 /* geometry of the BGR frames handed to uwip_strip_add */
+    int32_t  batch, max_frames;          /* most frames per add; capacity of the strip (frames are kept at working size) */
+    int32_t  max_canvas_rows, max_canvas_cols;   /* default 16384 x 16384 */
+    float    max_scale;                  /* default 4 */
+    uint32_t detect_flags, match_flags, seed;    /* as uwip_pipe_config; defaults = the reference's rules, seed 1 */
+    int32_t  videoWidth, videoHeight;    /* 0 = cols / rows */
+} uwip_strip_config;
+typedef struct uwip_strip_segment { int32_t first, count, x0, y0, rows, cols, reserved[2]; } uwip_strip_segment;
+#define UWIP_STRIP_FEATHER 0   /* weights 1 + distance to the frame's border, the default */
+#define UWIP_STRIP_FIRST   1   /* the covering frame with the smallest index */
+#define UWIP_STRIP_LAST    2   /* the covering frame with the largest index */
+int uwip_strip_config_default(uwip_strip_config *cfg, int rows, int cols);       /* batch 16, 1024 frames */
+int uwip_strip_create(uwip_ctx *ctx, const uwip_strip_config *cfg, uwip_strip **out);
+int uwip_strip_destroy(uwip_strip *s);          /* drains the stream first */
+int uwip_strip_reset(uwip_strip *s);            /* forget every frame: a new video */
+int uwip_strip_count(const uwip_strip *s, int *n);
+const char *uwip_strip_last_error(const uwip_strip *s);
+/* Append frames->frames (1..batch) frames of the configured geometry, the key frames main.cpp:368-381 writes.  The frames are
+ * resized into the strip's store (uwip_resize_bgr), detected into feature slots 1..n (slot 0 carries the previous call's last
+ * frame, the `struct keyframe` cache of videostrip.hpp:62-68), matched (i, i - 1) in one launch (videostrip.cpp:229-270), and
+ * the pairs' H and ratio are appended.  With d_H_inject [n][9] f64 and d_ratio_inject [n] f32 (device; both or neither) detect
+ * and match are skipped and those are appended instead, and the frames are stored AS GIVEN, without the resize: injected
+ * homographies are in the coordinates of the frames they come with (the parity hook, as uwip_dehaze's d_B_inject).  A strip
+ * takes one of the two forms from its first add until uwip_strip_reset.  Entry 0 of a strip's first add is not read.
+ * Asynchronous.  More than max_frames frames in total: UWIP_ERR_INVALID, and nothing is queued. */
+int uwip_strip_add(uwip_strip *s, const uwip_batch_u8 *frames, const double *d_H_inject, const float *d_ratio_inject);
+/* Chain and lay out what has been added (k_strip_chain), wait, and return the segments, up to `cap` (>= 1) of them per call
+ * (*n = how many; call again while *n == cap for the following ones -- a call that returns fewer ends the listing, and
+ * the next call starts from segment 0 again; so does the first call after an add). */
+int uwip_strip_layout(uwip_strip *s, uwip_strip_segment *h_segs, int cap, int *n);
+/* Parity tap, after uwip_strip_layout: h_G / h_Ginv [count][9] f64, h_seg [count] i32, h_box [count][4] i32 (x0, y0, x1, y1 on
+ * the segment's canvas, inclusive); any may be NULL.  Waits for the stream. */
+int uwip_strip_transforms(uwip_strip *s, double *h_G, double *h_Ginv, int32_t *h_seg, int32_t *h_box);
+/* Render one segment of the last layout into `canvas`: one frame, 3 channels, the segment's rows x cols, any step / base.
+ * fill [3] (NULL = black) is what uncovered pixels take; d_cover (may be NULL) [rows][cols] u8, packed: the number of frames
+ * that cover each pixel, saturating at 255.  Asynchronous. */
+int uwip_strip_render(uwip_strip *s, int segment, int mode, const uint8_t *fill, const uwip_batch_u8 *canvas, uint8_t *d_cover);
+/* The chain by itself on the host (csrc/strip_core.hpp, the source k_strip_chain runs), no device needed: what
+ * uwip_keyframe_chain_host is to the selector.  w x h: the stored frames; h_H [n][9], h_ratio [n]; outputs as
+ * uwip_strip_transforms and uwip_strip_layout (h_segs: up to cap entries, *n_segs = all). */
+int uwip_strip_chain_host(int w, int h, int max_canvas_rows, int max_canvas_cols, float max_scale, const double *h_H,
+                          const float *h_ratio, int n, double *h_G, double *h_Ginv, int32_t *h_seg, int32_t *h_box,
+                          uwip_strip_segment *h_segs, int cap, int *n_segs);
+
 #ifdef __cplusplus
 }
 #endif

@@ -37,7 +37,12 @@ public:
         int rc = uwip_ctx_create(device, nullptr, &ctx_);
         if (rc != UWIP_OK) throw Error(rc, "uwip_ctx_create failed: no HIP device (there is no CPU fallback)");
     }
-    ~Context() { uwip_ctx_destroy(ctx_); }
+    // a view of a context the caller owns (a program written against the C ABI that uses one of the classes below)
+    explicit Context(uwip_ctx *borrowed) : ctx_(borrowed), owned_(false)
+    {
+        if (!borrowed) throw Error(UWIP_ERR_INVALID, "null context");
+    }
+    ~Context() { if (owned_) uwip_ctx_destroy(ctx_); }
     Context(const Context &) = delete;
     Context &operator=(const Context &) = delete;
     uwip_ctx *get() const { return ctx_; }
@@ -45,6 +50,7 @@ public:
     static int deviceCount() { int n = 0; uwip_device_count(&n); return n; }   // cuda::getCudaEnabledDeviceCount
 private:
     uwip_ctx *ctx_ = nullptr;
+    bool owned_ = true;
 };
 
 // The rank's copy engine (uwip_copier): upload / download of frame batches between page-locked host buffers and HBM on
@@ -232,6 +238,58 @@ private:
     Context &c_;
     uwip_features *obj_ = nullptr;
     void *scratch_ = nullptr;
+};
+
+// ---- the strip mosaic of the key frames (uwip_strip, include/uwip.h) ---------------------------------------------------
+// add() takes each key frame where main.cpp:294,377 writes it; layout() chains the homographies of videostrip.cpp:270 and
+// returns the segments; render() gives one segment's canvas (`store` receives its pixels, as Videostrip::resize's does).
+class Strip {
+public:
+    // rows x cols: the full-resolution key frames; match_flags / detect_flags as Videostrip's
+    Strip(Context &c, int rows, int cols, int max_frames = 1024, unsigned detect_flags = 0, unsigned match_flags = 0) : c_(c)
+    {
+        uwip_strip_config cfg;
+        c_.check(uwip_strip_config_default(&cfg, rows, cols));
+        cfg.batch = 1; cfg.max_frames = max_frames; cfg.detect_flags = detect_flags; cfg.match_flags = match_flags;
+        c_.check(uwip_strip_create(c_.get(), &cfg, &s_));
+    }
+    ~Strip() { uwip_strip_destroy(s_); }
+    Strip(const Strip &) = delete;
+    Strip &operator=(const Strip &) = delete;
+    uwip_strip *get() const { return s_; }
+    int count() const { int n = 0; check(uwip_strip_count(s_, &n)); return n; }
+    void add(const Mat &frame)
+    {
+        DeviceMat d(c_, frame);
+        check(uwip_strip_add(s_, d.batch(), nullptr, nullptr));
+        c_.check(uwip_sync(c_.get()));                            // the device copy of the frame goes with this scope
+    }
+    std::vector<uwip_strip_segment> layout()
+    {
+        std::vector<uwip_strip_segment> segs, part(64);
+        for (int n = 64; n == 64;) {
+            check(uwip_strip_layout(s_, part.data(), 64, &n));
+            segs.insert(segs.end(), part.begin(), part.begin() + n);
+        }
+        segs_ = segs;
+        return segs;
+    }
+    // one segment of the last layout(); mode = UWIP_STRIP_FEATHER / FIRST / LAST
+    void render(int segment, int mode, Mat &out, std::vector<uint8_t> &store)
+    {
+        if (segment < 0 || segment >= (int)segs_.size()) throw Error(UWIP_ERR_INVALID, "Strip::render: no such segment (layout() first)");
+        const uwip_strip_segment &g = segs_[segment];
+        store.resize((size_t)g.rows * g.cols * 3);
+        out.data = store.data(); out.rows = g.rows; out.cols = g.cols; out.chans = 3; out.step = (size_t)g.cols * 3;
+        DeviceMat d(c_, g.rows, g.cols, 3);
+        check(uwip_strip_render(s_, segment, mode, nullptr, d.batch(), nullptr));
+        d.download(out);
+    }
+private:
+    void check(int rc) const { if (rc != UWIP_OK) throw Error(rc, uwip_strip_last_error(s_)); }
+    Context &c_;
+    uwip_strip *s_ = nullptr;
+    std::vector<uwip_strip_segment> segs_;
 };
 
 // ---- cv::imwrite(".jpg") / cv::imencode(".jpg") on the device ------------------------------------------------------

@@ -1,0 +1,130 @@
+#!/usr/bin/env python3
+"""What the strip mosaic costs on the device: 64 frames of 360 x 640 chained 128 px apart (injected translations), rendered
+after warm-up at least 20 times per mode; k_strip_render is timed by the library's per-kernel device events
+(uwip_prof_enable).  Reported: ms per render, canvas megapixels/s, covered pixel-frames/s, and the ratio to a
+device-to-device copy of the algorithmic bytes (canvas written plus frames read) timed in the same run; `add` per frame
+through detect and match (uw_stream frames, wall clock around a drained stream) and `layout` (wall clock).
+Culling: a render visits the frames of its own segment only, so frames of other segments cost nothing by construction (a
+segment's canvas is the box of all its frames: none of them lies outside it).  What culling costs inside a segment is
+measured on one of 1024 frames 15 px apart: every tile tests 1024 boxes in four chunks and lists about 47 of them.
+usage: python tools/strip_cost.py [--repeats 20] [--out profiles/strip_cost.json]"""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+import uwimageproc_amd as uw  # noqa: E402
+from uwimageproc_amd import synth  # noqa: E402
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--repeats", type=int, default=20)
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "strip_cost.json"))
+    a = ap.parse_args()
+    reps = max(20, a.repeats)
+    n, rows, cols, pitch = 64, 360, 640, 128
+    ctx = uw.Context(0)
+    rng = np.random.default_rng(1)
+    frames = torch.from_numpy(rng.integers(0, 256, (n, rows, cols, 3), dtype=np.uint8)).cuda()
+    H = np.tile(np.array([1.0, 0, float(pitch), 0, 1.0, 0, 0, 0, 1.0]), (n, 1))
+    s = uw.Strip(ctx, rows, cols, batch=16, max_frames=n)
+    dH, dr = torch.from_numpy(H).cuda(), torch.full((n,), 0.5, dtype=torch.float32, device="cuda")
+    for k in range(0, n, 16):
+        s.add(frames[k:k + 16], dH[k:k + 16].contiguous(), dr[k:k + 16].contiguous())
+    t0 = time.perf_counter()
+    seg = s.layout()[0]
+    layout_ms = (time.perf_counter() - t0) * 1e3
+    assert seg.count == n and seg.cols == cols + (n - 1) * pitch and seg.rows == rows
+    out = {"frames": n, "frame": [rows, cols], "pitch_px": pitch, "canvas": [seg.rows, seg.cols], "repeats": reps, "layout_ms_wall": layout_ms,
+           "render": {},
+           "cull_1024_frames_960_outside": "frames outside a segment are never visited: 0 by construction"}
+    canvas = torch.empty((seg.rows, seg.cols, 3), dtype=torch.uint8, device="cuda")
+    for mode in ("feather", "first", "last"):
+        _, cover = s.render(0, mode, cover=True, out=canvas)
+        covered = int(cover.to(torch.int64).sum())
+        for _ in range(3):
+            s.render(0, mode, out=canvas)
+        ctx.prof_enable(True)
+        ctx.prof_reset()
+        for _ in range(reps):
+            s.render(0, mode, out=canvas)
+        ms, launches = ctx.prof_results()["k_strip_render"]
+        ctx.prof_enable(False)
+        ms /= launches
+        out["render"][mode] = {"ms": ms, "canvas_mpix_per_s": seg.rows * seg.cols / ms / 1e3, "covered_pixel_frames_per_s": covered / ms * 1e3,
+                               "covered_pixel_frames": covered}
+    # the device-to-device copy of the algorithmic bytes: the canvas written plus every frame read once
+    nbytes = seg.rows * seg.cols * 3 + n * rows * cols * 3
+    src, dst = torch.empty(nbytes, dtype=torch.uint8, device="cuda"), torch.empty(nbytes, dtype=torch.uint8, device="cuda")
+    for _ in range(3):
+        dst.copy_(src)
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(reps):
+        dst.copy_(src)
+    e1.record()
+    torch.cuda.synchronize()
+    copy_ms = e0.elapsed_time(e1) / reps
+    out["d2d_copy"] = {"bytes": nbytes, "ms": copy_ms, "gb_per_s": 2 * nbytes / copy_ms / 1e6}
+    for mode in out["render"]:
+        out["render"][mode]["ratio_to_d2d_copy"] = out["render"][mode]["ms"] / copy_ms
+    s.close()
+    del frames, canvas, src, dst
+    # culling inside a segment: 1024 frames 15 px apart
+    n2, pitch2 = 1024, 15
+    f2 = torch.from_numpy(rng.integers(0, 256, (16, rows, cols, 3), dtype=np.uint8)).cuda()
+    H2 = torch.from_numpy(np.tile(np.array([1.0, 0, float(pitch2), 0, 1.0, 0, 0, 0, 1.0]), (16, 1))).cuda()
+    r2 = torch.full((16,), 0.5, dtype=torch.float32, device="cuda")
+    s = uw.Strip(ctx, rows, cols, batch=16, max_frames=n2)
+    for k in range(0, n2, 16):
+        s.add(f2, H2, r2)
+    seg2 = s.layout()[0]
+    assert seg2.count == n2 and seg2.cols == cols + (n2 - 1) * pitch2
+    canvas2 = torch.empty((seg2.rows, seg2.cols, 3), dtype=torch.uint8, device="cuda")
+    _, cover2 = s.render(0, "feather", cover=True, out=canvas2)
+    covered2 = n2 * rows * cols                              # every frame lies wholly inside (the cover plane saturates at 255)
+    s.render(0, "feather", out=canvas2)
+    ctx.prof_enable(True)
+    ctx.prof_reset()
+    for _ in range(reps):
+        s.render(0, "feather", out=canvas2)
+    ms2, l2 = ctx.prof_results()["k_strip_render"]
+    ctx.prof_enable(False)
+    ms2 /= l2
+    f64 = out["render"]["feather"]
+    out["cull_in_segment_1024_frames"] = {"canvas": [seg2.rows, seg2.cols], "pitch_px": pitch2, "ms": ms2, "covered_pixel_frames": covered2,
+                                          "ns_per_covered_pixel_frame": ms2 * 1e6 / covered2,
+                                          "ns_per_covered_pixel_frame_64_frames": f64["ms"] * 1e6 / f64["covered_pixel_frames"]}
+    s.close()
+    del f2, canvas2, cover2
+    # add through resize, detect and match: 16 frames per call, the stream drained around the timed calls
+    m = 48
+    stream = torch.from_numpy(synth.uw_stream(0, m, rows, cols, step_frac=0.2)).cuda()
+    s = uw.Strip(ctx, rows, cols, batch=16, max_frames=m)
+    s.add(stream[:16])                                       # warm-up: workspaces, tables
+    t0 = time.perf_counter()
+    s.add(stream[16:32])
+    s.add(stream[32:48])
+    out["add_ms_per_frame_wall"] = (time.perf_counter() - t0) * 1e3 / 32
+    t0 = time.perf_counter()
+    segs = s.layout()
+    out["layout_48_frames_ms_wall"] = (time.perf_counter() - t0) * 1e3
+    out["matched_segments"] = [[g.first, g.count, g.rows, g.cols] for g in segs]
+    s.close()
+    ctx.close()
+    os.makedirs(os.path.dirname(a.out), exist_ok=True)
+    with open(a.out, "w") as f:
+        json.dump(out, f, indent=1)
+        f.write("\n")
+    print(json.dumps(out))
+
+
+if __name__ == "__main__":
+    main()

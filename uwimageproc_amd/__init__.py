@@ -9,5 +9,6 @@ no CPU fallback.
 from ._native import BatchU8, Context, Copier, PipeConfig, UwipError, batch_of, device_count, lib  # noqa: F401
 from . import jpeg  # noqa: F401
 from . import png  # noqa: F401
+from .strip import Strip  # noqa: F401
 
-__all__ = ["BatchU8", "Context", "Copier", "PipeConfig", "UwipError", "batch_of", "device_count", "jpeg", "lib", "png"]
+__all__ = ["BatchU8", "Context", "Copier", "PipeConfig", "Strip", "UwipError", "batch_of", "device_count", "jpeg", "lib", "png"]

@@ -97,6 +97,22 @@ class StreamOut(C.Structure):
     _fields_ = [("index", C.c_int32), ("row_id", C.c_int32), ("size", C.c_int64), ("offset", C.c_int64)]
 
 
+class StripConfig(C.Structure):
+    """Mirror of ``uwip_strip_config``."""
+
+    _fields_ = [("rows", C.c_int32), ("cols", C.c_int32), ("batch", C.c_int32), ("max_frames", C.c_int32),
+                ("max_canvas_rows", C.c_int32), ("max_canvas_cols", C.c_int32), ("max_scale", C.c_float),
+                ("detect_flags", C.c_uint32), ("match_flags", C.c_uint32), ("seed", C.c_uint32),
+                ("videoWidth", C.c_int32), ("videoHeight", C.c_int32)]
+
+
+class StripSegment(C.Structure):
+    """Mirror of ``uwip_strip_segment`` (32 bytes)."""
+
+    _fields_ = [("first", C.c_int32), ("count", C.c_int32), ("x0", C.c_int32), ("y0", C.c_int32), ("rows", C.c_int32),
+                ("cols", C.c_int32), ("reserved", C.c_int32 * 2)]
+
+
 # uwip_keyframe_chain_host's callbacks
 KF_OVERLAP_FN = C.CFUNCTYPE(C.c_float, C.c_void_p, C.c_int32, C.c_int32)
 KF_BLUR_FN = C.CFUNCTYPE(C.c_float, C.c_void_p, C.c_int32)
@@ -219,6 +235,18 @@ SIGNATURES = {
     "uwip_png_info": (C.c_int, [_P, C.c_size_t, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "uwip_png_decode": (C.c_int, [_P, _P, _P, C.c_int, _B, _P, _P]),
     "uwip_png_decode_host": (C.c_int, [_P, _P, _P, C.c_int, _B, _P, _P]),
+    "uwip_strip_config_default": (C.c_int, [C.POINTER(StripConfig), C.c_int, C.c_int]),
+    "uwip_strip_create": (C.c_int, [_P, C.POINTER(StripConfig), C.POINTER(_P)]),
+    "uwip_strip_destroy": (C.c_int, [_P]),
+    "uwip_strip_reset": (C.c_int, [_P]),
+    "uwip_strip_count": (C.c_int, [_P, C.POINTER(C.c_int)]),
+    "uwip_strip_last_error": (C.c_char_p, [_P]),
+    "uwip_strip_add": (C.c_int, [_P, _B, _P, _P]),
+    "uwip_strip_layout": (C.c_int, [_P, C.POINTER(StripSegment), C.c_int, C.POINTER(C.c_int)]),
+    "uwip_strip_transforms": (C.c_int, [_P, _P, _P, _P, _P]),
+    "uwip_strip_render": (C.c_int, [_P, C.c_int, C.c_int, _P, _B, _P]),
+    "uwip_strip_chain_host": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, _P, _P, C.c_int, _P, _P, _P, _P,
+                                        C.POINTER(StripSegment), C.c_int, C.POINTER(C.c_int)]),
 }
 
 

@@ -1,0 +1,455 @@
+// Strip mosaic (include/uwip.h, "strip mosaic"): the key frames of main.cpp:368-381, chained by the
+// homographies of videostrip.cpp:270 and rendered into one canvas per segment.
+//   k_strip_chain    one lane runs strip_core.hpp's chain() over the appended H / ratio arrays;
+//   k_strip_render   canvas-centric gather: a workgroup owns a 64 x 16 tile, collects the frames whose box meets it (in
+//                    chunks of kCullChunk, compacted in LDS together with their inverse transforms), every thread keeps
+//                    integer accumulators for its four pixels, the tile is assembled in LDS and written row by row;
+//   k_strip_store    the injected form's copy of frames into the store.
+// Everything inside the anonymous namespace is also compiled by the host compiler and run on host threads by
+// tests/strip_emulated.cpp (no HIP-only intrinsics in there).
+#include "uwip_internal.hpp"
+#include "strip_core.hpp"
+#include <algorithm>
+#include <cstring>
+
+namespace {
+constexpr int kTileW = 64, kTileH = 16, kRenderThreads = 256;
+constexpr int kPix = kTileW * kTileH / kRenderThreads;      // pixels per thread: rows ly, ly + 4, ly + 8, ly + 12 of one column
+constexpr int kCullChunk = 256;                              // frames tested (and at most listed) per pass of the cull list
+constexpr int kTileRowBytes = kTileW * 3;
+
+struct StripRender {
+    const uint8_t *store;                 // [frames][h][w][3]
+    size_t fstride;
+    int32_t w, h;
+    const double *Ginv;                   // [frames][9]
+    const int32_t *box;                   // [frames][4]
+    int32_t first, count;                 // the segment's frames
+    int32_t x0, y0, rows, cols;           // the segment's canvas
+    uint8_t *canvas;
+    size_t step;
+    uint8_t *cover;                       // [rows][cols] or null
+    uint8_t fill[4];
+    int32_t vec;                          // bytes per store of the write-out: 16, 4 or 1
+};
+
+__global__ __launch_bounds__(64) void k_strip_chain(uwip_sm::ChainParams P, const double *H, const float *ratio, int32_t n,
+                                                    uwip_sm::ChainOut o, double *fb)
+{
+    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+    uwip_sm::chain(P, H, ratio, n, o, fb);
+}
+
+__global__ __launch_bounds__(256) void k_strip_store(const uint8_t *src, size_t step, size_t fs, int32_t rows, int32_t rowbytes,
+                                                     uint8_t *dst)
+{
+    const int32_t x = (int32_t)(blockIdx.x * blockDim.x + threadIdx.x), y = (int32_t)blockIdx.y;
+    const size_t f = blockIdx.z;
+    if (x < rowbytes && y < rows) dst[(f * rows + y) * (size_t)rowbytes + x] = src[f * fs + (size_t)y * step + x];
+}
+
+template <int MODE>
+__global__ __launch_bounds__(kRenderThreads) void k_strip_render(StripRender a)
+{
+    __shared__ double s_A[kCullChunk][9];
+    __shared__ int32_t s_idx[kCullChunk];
+    __shared__ uint32_t s_n;
+    __shared__ uint32_t s_tile[kTileH * kTileRowBytes / 4];
+    const int32_t tid = (int32_t)threadIdx.x;
+    const int32_t tx0 = (int32_t)blockIdx.x * kTileW, ty0 = (int32_t)blockIdx.y * kTileH;
+    const int32_t tx1 = min(tx0 + kTileW, a.cols) - 1, ty1 = min(ty0 + kTileH, a.rows) - 1;
+    const int32_t lx = tid & (kTileW - 1), ly = tid / kTileW;
+    const int32_t X = tx0 + lx;
+    const double px = (double)(X + a.x0);
+
+    // FEATHER: num / den; FIRST / LAST: the winner's index in den and its P in num
+    int64_t num[kPix][3], den[kPix];
+    uint32_t cnt[kPix];
+#pragma unroll
+    for (int j = 0; j < kPix; ++j) { num[j][0] = num[j][1] = num[j][2] = 0; den[j] = MODE == UWIP_STRIP_FEATHER ? 0 : -1; cnt[j] = 0; }
+
+    for (int32_t base = 0; base < a.count; base += kCullChunk) {
+        __syncthreads();                                   // the previous chunk's list has been read by everyone
+        if (tid == 0) s_n = 0;
+        __syncthreads();
+        for (int32_t k = base + tid; k < min(base + kCullChunk, a.count); k += kRenderThreads) {
+            const int32_t g = a.first + k;
+            const int32_t *b = a.box + 4 * (size_t)g;
+            if (b[0] <= tx1 && b[2] >= tx0 && b[1] <= ty1 && b[3] >= ty0) {
+                const uint32_t slot = atomicAdd(&s_n, 1u);
+                s_idx[slot] = g;
+                for (int i = 0; i < 9; ++i) s_A[slot][i] = a.Ginv[9 * (size_t)g + i];
+            }
+        }
+        __syncthreads();
+        const int32_t n = (int32_t)s_n;
+        if (X > tx1) continue;                             // a column beyond the canvas: nothing to accumulate (barriers stay uniform)
+        for (int32_t e = 0; e < n; ++e) {
+            double A[9];
+#pragma unroll
+            for (int i = 0; i < 9; ++i) A[i] = s_A[e][i];
+            const int32_t g = s_idx[e];
+            const uint8_t *f = a.store + (size_t)g * a.fstride;
+#pragma unroll
+            for (int j = 0; j < kPix; ++j) {
+                const int32_t Y = ty0 + ly + j * (kRenderThreads / kTileW);
+                if (Y > ty1) continue;
+                uwip_sm::Tap t;
+                if (!uwip_sm::sample(A, px, (double)(Y + a.y0), a.w, a.h, t)) continue;
+                cnt[j] += 1u;
+                if (MODE != UWIP_STRIP_FEATHER) {
+                    const bool wins = den[j] < 0 || (MODE == UWIP_STRIP_LAST ? g > den[j] : g < den[j]);
+                    if (!wins) continue;
+                    den[j] = g;
+                }
+                const uint8_t *r0 = f + ((size_t)t.y * a.w) * 3, *r1 = f + ((size_t)t.y1 * a.w) * 3;
+#pragma unroll
+                for (int c = 0; c < 3; ++c) {
+                    const int32_t P = uwip_sm::bilinear(t, r0[t.x * 3 + c], r0[t.x1 * 3 + c], r1[t.x * 3 + c], r1[t.x1 * 3 + c]);
+                    if (MODE == UWIP_STRIP_FEATHER) num[j][c] += (int64_t)t.q * P;
+                    else num[j][c] = P;
+                }
+                if (MODE == UWIP_STRIP_FEATHER) den[j] += t.q;
+            }
+        }
+    }
+
+    // the tile in LDS, then its rows out contiguously
+    uint8_t *tile = reinterpret_cast<uint8_t *>(s_tile);
+#pragma unroll
+    for (int j = 0; j < kPix; ++j) {
+        const int32_t r = ly + j * (kRenderThreads / kTileW), Y = ty0 + r;
+        if (X > tx1 || Y > ty1) continue;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            uint8_t v = a.fill[c];
+            if (MODE == UWIP_STRIP_FEATHER) {
+                if (den[j] > 0) v = (uint8_t)((num[j][c] + 512 * den[j]) / (1024 * den[j]));
+            } else if (den[j] >= 0) {
+                v = (uint8_t)((num[j][c] + 512) >> 10);
+            }
+            tile[r * kTileRowBytes + lx * 3 + c] = v;
+        }
+        if (a.cover) a.cover[(size_t)Y * a.cols + X] = (uint8_t)(cnt[j] > 255u ? 255u : cnt[j]);
+    }
+    __syncthreads();
+    const int32_t th = ty1 - ty0 + 1, nb = (tx1 - tx0 + 1) * 3;       // rows of this tile, bytes of each
+    uint8_t *out = a.canvas + (size_t)ty0 * a.step + (size_t)tx0 * 3;
+    if (a.vec == 16) {
+        constexpr int U = kTileRowBytes / 16;
+        for (int32_t i = tid; i < kTileH * U; i += kRenderThreads) {
+            const int32_t r = i / U, at = (i % U) * 16;
+            if (r >= th || at >= nb) continue;
+            uint8_t *p = out + (size_t)r * a.step + at;
+            const uint32_t *s = s_tile + (r * kTileRowBytes + at) / 4;
+            if (at + 16 <= nb) *reinterpret_cast<uint4 *>(p) = make_uint4(s[0], s[1], s[2], s[3]);
+            else for (int32_t q = at; q < nb; ++q) out[(size_t)r * a.step + q] = tile[r * kTileRowBytes + q];
+        }
+    } else if (a.vec == 4) {
+        constexpr int U = kTileRowBytes / 4;
+        for (int32_t i = tid; i < kTileH * U; i += kRenderThreads) {
+            const int32_t r = i / U, at = (i % U) * 4;
+            if (r >= th || at >= nb) continue;
+            uint8_t *p = out + (size_t)r * a.step + at;
+            if (at + 4 <= nb) *reinterpret_cast<uint32_t *>(p) = s_tile[(r * kTileRowBytes + at) / 4];
+            else for (int32_t q = at; q < nb; ++q) out[(size_t)r * a.step + q] = tile[r * kTileRowBytes + q];
+        }
+    } else {
+        for (int32_t i = tid; i < kTileH * kTileRowBytes; i += kRenderThreads) {
+            const int32_t r = i / kTileRowBytes, at = i % kTileRowBytes;
+            if (r < th && at < nb) out[(size_t)r * a.step + at] = tile[i];
+        }
+    }
+}
+}  // namespace
+
+struct uwip_strip {
+    uwip_ctx *ctx = nullptr;
+    uwip_strip_config cfg{};
+    std::string err;
+    int form = 0;                          // 0: no frame yet; 1: resized, detected, matched; 2: injected, stored as given
+    int w = 0, h = 0;                      // geometry of the stored frames (the working size, or rows x cols when injected)
+    int count = 0, last_n = 0;
+    bool have_prev = false;
+    uint8_t *store = nullptr;
+    size_t store_bytes = 0;
+    uint8_t *block = nullptr;              // the chain's arrays, one allocation
+    double *H = nullptr, *G = nullptr, *Ginv = nullptr, *fb = nullptr;
+    float *ratio = nullptr;
+    int32_t *seg = nullptr, *box = nullptr, *nseg = nullptr;
+    uwip_strip_segment *segs = nullptr;
+    uwip_features *feats = nullptr;
+    std::vector<int32_t> pq, pt;
+    std::vector<uwip_strip_segment> h_segs;    // the last layout
+    int laid = -1;                         // frame count the last layout saw (-1: none)
+    int cursor = 0;                        // next segment uwip_strip_layout returns
+
+    int fail(int code, const char *what) { err = what; return code; }
+    int from_ctx(int rc) { if (rc) err = ctx->err; return rc; }
+};
+
+static bool strip_config_ok(const uwip_strip_config &c)
+{
+    return c.rows >= 2 && c.cols >= 2 && c.rows <= 32768 && c.cols <= 32768 && c.batch >= 1 && c.batch <= 4094 && c.max_frames >= 1 &&
+           c.max_canvas_rows >= 1 && c.max_canvas_cols >= 1 && c.max_canvas_rows <= 32768 && c.max_canvas_cols <= 32768 &&
+           c.max_scale >= 1.0f && c.max_scale <= 1024.0f && c.videoWidth >= 0 && c.videoHeight >= 0;
+}
+
+UWIP_API int uwip_strip_config_default(uwip_strip_config *cfg, int rows, int cols)
+{
+    if (!cfg || rows < 2 || cols < 2) return UWIP_ERR_INVALID;
+    std::memset(cfg, 0, sizeof *cfg);
+    cfg->rows = rows; cfg->cols = cols;
+    cfg->batch = 16; cfg->max_frames = 1024;
+    cfg->max_canvas_rows = cfg->max_canvas_cols = 16384;
+    cfg->max_scale = 4.0f;
+    cfg->seed = 1;
+    return UWIP_OK;
+}
+
+static size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
+
+UWIP_API int uwip_strip_create(uwip_ctx *ctx, const uwip_strip_config *cfg, uwip_strip **out)
+{
+    if (!ctx || !out) return UWIP_ERR_INVALID;
+    *out = nullptr;
+    if (int rc_e = uwip_enter(ctx)) return rc_e;
+    UWIP_REQUIRE(ctx, cfg != nullptr && strip_config_ok(*cfg), "bad strip configuration");
+    uwip_strip *s = new uwip_strip;
+    s->ctx = ctx; s->cfg = *cfg;
+    const size_t N = (size_t)cfg->max_frames;
+    size_t off = 0;
+    auto take = [&](size_t bytes) { const size_t at = off; off += align256(bytes); return at; };
+    const size_t o_H = take(72 * N), o_G = take(72 * N), o_Gi = take(72 * N), o_fb = take(32 * N), o_ratio = take(4 * N), o_seg = take(4 * N),
+                 o_box = take(16 * N), o_segs = take(sizeof(uwip_strip_segment) * N), o_nseg = take(4);
+    void *d = nullptr;
+    int rc = uwip_malloc(ctx, off, &d);
+    if (!rc) rc = uwip_features_create(ctx, cfg->batch + 1, &s->feats);
+    if (rc) {
+        if (d) uwip_free(ctx, d);
+        delete s;
+        return rc;
+    }
+    s->block = (uint8_t *)d;
+    s->H = (double *)(s->block + o_H); s->G = (double *)(s->block + o_G); s->Ginv = (double *)(s->block + o_Gi);
+    s->fb = (double *)(s->block + o_fb); s->ratio = (float *)(s->block + o_ratio); s->seg = (int32_t *)(s->block + o_seg);
+    s->box = (int32_t *)(s->block + o_box); s->segs = (uwip_strip_segment *)(s->block + o_segs); s->nseg = (int32_t *)(s->block + o_nseg);
+    s->pq.resize(cfg->batch); s->pt.resize(cfg->batch);
+    for (int i = 0; i < cfg->batch; ++i) { s->pq[i] = i + 1; s->pt[i] = i; }
+    *out = s;
+    return UWIP_OK;
+}
+
+UWIP_API int uwip_strip_destroy(uwip_strip *s)
+{
+    if (!s) return UWIP_OK;
+    if (uwip_enter(s->ctx) == UWIP_OK) (void)uwip_stream_wait(s->ctx);
+    if (s->feats) uwip_features_destroy(s->feats);
+    if (s->store) uwip_free(s->ctx, s->store);
+    if (s->block) uwip_free(s->ctx, s->block);
+    delete s;
+    return UWIP_OK;
+}
+
+UWIP_API int uwip_strip_reset(uwip_strip *s)
+{
+    if (!s) return UWIP_ERR_INVALID;
+    s->form = 0; s->count = 0; s->last_n = 0; s->have_prev = false; s->laid = -1; s->cursor = 0;
+    s->h_segs.clear();
+    return UWIP_OK;
+}
+
+UWIP_API int uwip_strip_count(const uwip_strip *s, int *n)
+{
+    if (!s || !n) return UWIP_ERR_INVALID;
+    *n = s->count;
+    return UWIP_OK;
+}
+
+UWIP_API const char *uwip_strip_last_error(const uwip_strip *s) { return s ? s->err.c_str() : "null strip"; }
+
+UWIP_API int uwip_strip_add(uwip_strip *s, const uwip_batch_u8 *frames, const double *d_H_inject, const float *d_ratio_inject)
+{
+    if (!s) return UWIP_ERR_INVALID;
+    uwip_ctx *ctx = s->ctx;
+    const uwip_strip_config &c = s->cfg;
+    int rc = uwip_check_batch(ctx, frames, 3);
+    if (rc) return s->from_ctx(rc);
+    if (frames->rows != c.rows || frames->cols != c.cols) return s->fail(UWIP_ERR_INVALID, "uwip_strip_add: not the configured frame geometry");
+    if (frames->frames < 1 || frames->frames > c.batch) return s->fail(UWIP_ERR_INVALID, "uwip_strip_add: 1..batch frames per call");
+    if ((d_H_inject == nullptr) != (d_ratio_inject == nullptr)) return s->fail(UWIP_ERR_INVALID, "uwip_strip_add: inject both H and ratio, or neither");
+    const int form = d_H_inject ? 2 : 1, n = frames->frames;
+    if (s->form && s->form != form) return s->fail(UWIP_ERR_INVALID, "uwip_strip_add: matched and injected frames do not mix in one strip");
+    if ((int64_t)s->count + n > c.max_frames) return s->fail(UWIP_ERR_INVALID, "uwip_strip_add: more than max_frames frames");
+    if (!s->form) {
+        // the first frame decides the store's geometry; the store is allocated here, once per form (a strip that is reset keeps it)
+        int w = c.cols, h = c.rows;
+        if (form == 1 && (rc = uwip_overlap_working_size(c.rows, c.cols, &h, &w))) return s->fail(rc, "uwip_overlap_working_size");
+        if (w > c.max_canvas_cols || h > c.max_canvas_rows) return s->fail(UWIP_ERR_INVALID, "uwip_strip_add: a frame is larger than the largest canvas");
+        const size_t need = (size_t)w * h * 3 * (size_t)c.max_frames;
+        if (need > s->store_bytes) {
+            if (s->store) {
+                UWIP_HIP(ctx, uwip_stream_wait(ctx));
+                uwip_free(ctx, s->store);
+                s->store = nullptr; s->store_bytes = 0;
+            }
+            void *d = nullptr;
+            if ((rc = uwip_malloc(ctx, need, &d))) return s->from_ctx(rc);
+            s->store = (uint8_t *)d; s->store_bytes = need;
+        }
+        s->w = w; s->h = h;
+    }
+    const size_t fbytes = (size_t)s->w * s->h * 3;
+    uwip_batch_u8 dst;
+    dst.data = s->store + (size_t)s->count * fbytes; dst.step = (size_t)s->w * 3; dst.frame_stride = fbytes;
+    dst.rows = s->h; dst.cols = s->w; dst.channels = 3; dst.frames = n;
+    if (form == 1) {
+        // cv::resize(frame, res_frame, Size(), f, f), main.cpp:242,311: the frames the homographies refer to
+        if ((rc = uwip_resize_bgr(ctx, frames, &dst))) return s->from_ctx(rc);
+        if (!s->have_prev) {
+            // a strip's first frame is its own predecessor, as the pipe's first frame is its own key frame (main.cpp:284-297):
+            // it is detected into slot 0 and again into slot 1, and the pair (1, 0) yields an H[0] the chain never reads.
+            // Deliberate: one pair list and one launch shape for every add, for one extra detect per strip
+            uwip_batch_u8 first = *frames;
+            first.frames = 1;
+            if ((rc = uwip_overlap_detect_ex(ctx, &first, s->feats, 0, c.detect_flags))) return s->from_ctx(rc);
+        } else if ((rc = uwip_features_copy(ctx, s->feats, s->last_n, s->feats, 0))) {
+            return s->from_ctx(rc);
+        }
+        if ((rc = uwip_overlap_detect_ex(ctx, frames, s->feats, 1, c.detect_flags))) return s->from_ctx(rc);
+        rc = uwip_overlap_match_ex(ctx, s->feats, s->feats, s->pq.data(), s->pt.data(), n, c.videoWidth ? c.videoWidth : c.cols,
+                                   c.videoHeight ? c.videoHeight : c.rows, c.seed, c.match_flags, s->ratio + s->count, nullptr,
+                                   s->H + 9 * (size_t)s->count, nullptr, nullptr);
+        if (rc) return s->from_ctx(rc);
+    } else {
+        const int32_t rowbytes = s->w * 3;
+        {
+            uwip_kscope ks(ctx, "k_strip_store");
+            k_strip_store<<<dim3(uwip_cdiv((size_t)rowbytes, 256), (unsigned)s->h, (unsigned)n), 256, 0, ctx->stream>>>(
+                (const uint8_t *)frames->data, frames->step, frames->frame_stride, s->h, rowbytes, (uint8_t *)dst.data);
+            UWIP_HIP(ctx, hipGetLastError());
+        }
+        UWIP_HIP(ctx, hipMemcpyAsync(s->H + 9 * (size_t)s->count, d_H_inject, 72 * (size_t)n, hipMemcpyDeviceToDevice, ctx->stream));
+        UWIP_HIP(ctx, hipMemcpyAsync(s->ratio + s->count, d_ratio_inject, 4 * (size_t)n, hipMemcpyDeviceToDevice, ctx->stream));
+    }
+    s->form = form; s->have_prev = true; s->last_n = n; s->count += n;
+    return UWIP_OK;
+}
+
+static uwip_sm::ChainParams chain_params(int w, int h, int max_rows, int max_cols, float max_scale)
+{
+    uwip_sm::ChainParams P;
+    P.w = w; P.h = h; P.max_rows = max_rows; P.max_cols = max_cols; P.max_scale = (double)max_scale;
+    return P;
+}
+
+// run the chain over what has been added and fetch the segments, unless the last layout is still current
+static int strip_lay_out(uwip_strip *s)
+{
+    uwip_ctx *ctx = s->ctx;
+    if (s->laid == s->count) return UWIP_OK;
+    s->h_segs.clear();
+    if (s->count > 0) {
+        uwip_sm::ChainOut o;
+        o.G = s->G; o.Ginv = s->Ginv; o.seg = s->seg; o.box = s->box; o.segs = s->segs; o.nseg = s->nseg;
+        {
+            uwip_kscope ks(ctx, "k_strip_chain");
+            k_strip_chain<<<1, 64, 0, ctx->stream>>>(chain_params(s->w, s->h, s->cfg.max_canvas_rows, s->cfg.max_canvas_cols, s->cfg.max_scale),
+                                                     s->H, s->ratio, s->count, o, s->fb);
+            UWIP_HIP(ctx, hipGetLastError());
+        }
+        int32_t nseg = 0;
+        int rc = uwip_memcpy_d2h(ctx, &nseg, s->nseg, 4);
+        if (rc) return rc;
+        if (nseg < 1 || nseg > s->count) return ctx->fail(UWIP_ERR_HIP, "k_strip_chain left no segment count");
+        s->h_segs.resize(nseg);
+        if ((rc = uwip_memcpy_d2h(ctx, s->h_segs.data(), s->segs, sizeof(uwip_strip_segment) * (size_t)nseg))) return rc;
+    }
+    s->laid = s->count;
+    return UWIP_OK;
+}
+
+UWIP_API int uwip_strip_layout(uwip_strip *s, uwip_strip_segment *h_segs, int cap, int *n)
+{
+    if (!s) return UWIP_ERR_INVALID;
+    if (!h_segs || !n || cap < 1) return s->fail(UWIP_ERR_INVALID, "uwip_strip_layout: h_segs, n and cap >= 1");
+    *n = 0;
+    if (int rc_e = uwip_enter(s->ctx)) return s->from_ctx(rc_e);
+    if (s->laid != s->count) s->cursor = 0;                 // frames were added: the listing starts over
+    if (int rc = strip_lay_out(s)) return s->from_ctx(rc);
+    const int total = (int)s->h_segs.size(), at = std::min(s->cursor, total), k = std::min(cap, total - at);
+    std::copy(s->h_segs.begin() + at, s->h_segs.begin() + at + k, h_segs);
+    *n = k;
+    s->cursor = k == cap ? at + k : 0;
+    return UWIP_OK;
+}
+
+UWIP_API int uwip_strip_transforms(uwip_strip *s, double *h_G, double *h_Ginv, int32_t *h_seg, int32_t *h_box)
+{
+    if (!s) return UWIP_ERR_INVALID;
+    if (int rc_e = uwip_enter(s->ctx)) return s->from_ctx(rc_e);
+    if (s->laid != s->count) return s->fail(UWIP_ERR_INVALID, "uwip_strip_transforms: call uwip_strip_layout first");
+    const size_t N = (size_t)s->count;
+    int rc = UWIP_OK;
+    if (!rc && h_G) rc = uwip_memcpy_d2h(s->ctx, h_G, s->G, 72 * N);
+    if (!rc && h_Ginv) rc = uwip_memcpy_d2h(s->ctx, h_Ginv, s->Ginv, 72 * N);
+    if (!rc && h_seg) rc = uwip_memcpy_d2h(s->ctx, h_seg, s->seg, 4 * N);
+    if (!rc && h_box) rc = uwip_memcpy_d2h(s->ctx, h_box, s->box, 16 * N);
+    return s->from_ctx(rc);
+}
+
+UWIP_API int uwip_strip_render(uwip_strip *s, int segment, int mode, const uint8_t *fill, const uwip_batch_u8 *canvas, uint8_t *d_cover)
+{
+    if (!s) return UWIP_ERR_INVALID;
+    uwip_ctx *ctx = s->ctx;
+    int rc = uwip_check_batch(ctx, canvas, 3);
+    if (rc) return s->from_ctx(rc);
+    if (s->laid != s->count || s->count == 0) return s->fail(UWIP_ERR_INVALID, "uwip_strip_render: call uwip_strip_layout first");
+    if (segment < 0 || segment >= (int)s->h_segs.size()) return s->fail(UWIP_ERR_INVALID, "uwip_strip_render: no such segment");
+    if (mode != UWIP_STRIP_FEATHER && mode != UWIP_STRIP_FIRST && mode != UWIP_STRIP_LAST) return s->fail(UWIP_ERR_INVALID, "uwip_strip_render: unknown mode");
+    const uwip_strip_segment &g = s->h_segs[segment];
+    if (canvas->frames != 1 || canvas->rows != g.rows || canvas->cols != g.cols)
+        return s->fail(UWIP_ERR_INVALID, "uwip_strip_render: the canvas is not one frame of the segment's rows x cols");
+    StripRender a;
+    a.store = s->store; a.fstride = (size_t)s->w * s->h * 3; a.w = s->w; a.h = s->h;
+    a.Ginv = s->Ginv; a.box = s->box; a.first = g.first; a.count = g.count;
+    a.x0 = g.x0; a.y0 = g.y0; a.rows = g.rows; a.cols = g.cols;
+    a.canvas = (uint8_t *)canvas->data; a.step = canvas->step; a.cover = d_cover;
+    for (int c = 0; c < 3; ++c) a.fill[c] = fill ? fill[c] : 0;
+    a.fill[3] = 0;
+    // the tile's rows start at multiples of 192 bytes from the row's start: base and step decide the store width
+    const uintptr_t al = (uintptr_t)canvas->data | (uintptr_t)canvas->step;
+    a.vec = al % 16 == 0 ? 16 : (al % 4 == 0 ? 4 : 1);
+    const dim3 grid(uwip_cdiv((size_t)g.cols, kTileW), uwip_cdiv((size_t)g.rows, kTileH));
+    uwip_kscope ks(ctx, "k_strip_render");
+    if (mode == UWIP_STRIP_FEATHER) k_strip_render<UWIP_STRIP_FEATHER><<<grid, kRenderThreads, 0, ctx->stream>>>(a);
+    else if (mode == UWIP_STRIP_FIRST) k_strip_render<UWIP_STRIP_FIRST><<<grid, kRenderThreads, 0, ctx->stream>>>(a);
+    else k_strip_render<UWIP_STRIP_LAST><<<grid, kRenderThreads, 0, ctx->stream>>>(a);
+    UWIP_HIP(ctx, hipGetLastError());
+    return UWIP_OK;
+}
+
+UWIP_API int uwip_strip_chain_host(int w, int h, int max_canvas_rows, int max_canvas_cols, float max_scale, const double *h_H,
+                                   const float *h_ratio, int n, double *h_G, double *h_Ginv, int32_t *h_seg, int32_t *h_box,
+                                   uwip_strip_segment *h_segs, int cap, int *n_segs)
+{
+    if (w < 2 || h < 2 || w > 32768 || h > 32768 || max_canvas_rows < h || max_canvas_cols < w || max_canvas_rows > 32768 ||
+        max_canvas_cols > 32768 || !(max_scale >= 1.0f) || max_scale > 1024.0f || n < 0 || (n > 0 && (!h_H || !h_ratio)) || !n_segs ||
+        cap < 0 || (cap > 0 && !h_segs))
+        return UWIP_ERR_INVALID;
+    const size_t N = (size_t)n;
+    std::vector<double> G(9 * N), Ginv(9 * N), fb(4 * N);
+    std::vector<int32_t> seg(N), box(4 * N);
+    std::vector<uwip_strip_segment> segs(N);
+    int32_t nseg = 0;
+    uwip_sm::ChainOut o;
+    o.G = G.data(); o.Ginv = Ginv.data(); o.seg = seg.data(); o.box = box.data(); o.segs = segs.data(); o.nseg = &nseg;
+    uwip_sm::chain(chain_params(w, h, max_canvas_rows, max_canvas_cols, max_scale), h_H, h_ratio, n, o, fb.data());
+    if (h_G) std::copy(G.begin(), G.end(), h_G);
+    if (h_Ginv) std::copy(Ginv.begin(), Ginv.end(), h_Ginv);
+    if (h_seg) std::copy(seg.begin(), seg.end(), h_seg);
+    if (h_box) std::copy(box.begin(), box.end(), h_box);
+    std::copy(segs.begin(), segs.begin() + std::min(nseg, cap), h_segs ? h_segs : segs.data());
+    *n_segs = nseg;
+    return UWIP_OK;
+}

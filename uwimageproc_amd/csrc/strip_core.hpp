@@ -1,0 +1,191 @@
+// The arithmetic of the strip mosaic, stated ONCE for the device (strip.hip: k_strip_chain, k_strip_render), the host
+// (uwip_strip_chain_host) and the emulation harness (tests/strip_emulated.cpp).  tests/_strip_mirror.py restates it in numpy
+// and takes nothing from here; the tests compare the two bit for bit, which is why
+//   - every coordinate is float64, products and sums are separate operations (the library and the harness are built with
+//     -ffp-contract=off), sums are written ((a*x) + (b*y)) + c, and divisions are IEEE divisions;
+//   - everything after the source position (u, v) is integer arithmetic.
+// Conventions: pixel centres at integer coordinates; frames are w x h BGR; H_k takes frame k onto frame k - 1 (the matcher's
+// d_H with query = k, train = k - 1, videostrip.cpp:270); G_k takes frame k onto the plane of its segment, which is the
+// coordinate system of the segment's first frame.
+#pragma once
+#include <cmath>
+#include <cstdint>
+#include "../../include/uwip.h"
+
+#if defined(__HIPCC__)
+#include <hip/hip_runtime.h>
+#define STRIP_HD __host__ __device__
+#else
+#define STRIP_HD
+#endif
+
+namespace uwip_sm {
+
+struct ChainParams {
+    int32_t w, h;                         // geometry of the stored frames
+    int32_t max_rows, max_cols;           // largest canvas of one segment
+    double  max_scale;                    // a frame's mapped area stays within (w-1)(h-1) / s^2 ... (w-1)(h-1) * s^2
+};
+
+// what the chain writes ([n] frames; segs holds one entry per segment, at most n)
+struct ChainOut {
+    double  *G, *Ginv;                    // [n][9]
+    int32_t *seg;                         // [n]
+    int32_t *box;                         // [n][4] = x0, y0, x1, y1 on the segment's canvas (inclusive, grown by 1, clamped)
+    uwip_strip_segment *segs;
+    int32_t *nseg;
+};
+
+STRIP_HD inline bool finite_d(double v) { return v - v == 0.0; }
+
+// adjugate of G times the sign of its determinant: the projective inverse with a positive denominator wherever G's own
+// denominator is positive.  Not divided by the determinant (a homography's scale is free).
+STRIP_HD inline void adjugate_signed(const double *G, double *A)
+{
+    A[0] = (G[4] * G[8]) - (G[5] * G[7]);
+    A[1] = (G[2] * G[7]) - (G[1] * G[8]);
+    A[2] = (G[1] * G[5]) - (G[2] * G[4]);
+    A[3] = (G[5] * G[6]) - (G[3] * G[8]);
+    A[4] = (G[0] * G[8]) - (G[2] * G[6]);
+    A[5] = (G[2] * G[3]) - (G[0] * G[5]);
+    A[6] = (G[3] * G[7]) - (G[4] * G[6]);
+    A[7] = (G[1] * G[6]) - (G[0] * G[7]);
+    A[8] = (G[0] * G[4]) - (G[1] * G[3]);
+    const double det = ((G[0] * A[0]) + (G[1] * A[3])) + (G[2] * A[6]);
+    const double s = det < 0.0 ? -1.0 : 1.0;
+    for (int i = 0; i < 9; ++i) A[i] = A[i] * s;
+}
+
+// Break rules 2-4 on a candidate G: maps the four pixel-centre corners; q = x0..x3, y0..y3.  false = start a new segment.
+STRIP_HD inline bool quad_ok(const ChainParams &P, const double *G, double *qx, double *qy)
+{
+    for (int i = 0; i < 9; ++i) if (!finite_d(G[i])) return false;
+    const double cx[4] = {0.0, (double)(P.w - 1), (double)(P.w - 1), 0.0};
+    const double cy[4] = {0.0, 0.0, (double)(P.h - 1), (double)(P.h - 1)};
+    for (int i = 0; i < 4; ++i) {
+        const double d = ((G[6] * cx[i]) + (G[7] * cy[i])) + G[8];
+        if (!(d > 0.0)) return false;
+        qx[i] = (((G[0] * cx[i]) + (G[1] * cy[i])) + G[2]) / d;
+        qy[i] = (((G[3] * cx[i]) + (G[4] * cy[i])) + G[5]) / d;
+        if (!finite_d(qx[i]) || !finite_d(qy[i])) return false;
+    }
+    // rule 3: strictly convex, the input's orientation (every cross product of consecutive edges > 0)
+    for (int i = 0; i < 4; ++i) {
+        const int j = (i + 1) & 3, k = (i + 2) & 3;
+        const double ax = qx[j] - qx[i], ay = qy[j] - qy[i], bx = qx[k] - qx[j], by = qy[k] - qy[j];
+        const double c = (ax * by) - (ay * bx);
+        if (!(c > 0.0)) return false;
+    }
+    // rule 4: shoelace area
+    double s = 0.0;
+    for (int i = 0; i < 4; ++i) {
+        const int j = (i + 1) & 3;
+        s = s + ((qx[i] * qy[j]) - (qx[j] * qy[i]));
+    }
+    const double area = 0.5 * s, a0 = (double)(P.w - 1) * (double)(P.h - 1), s2 = P.max_scale * P.max_scale;
+    if (!(area >= a0 / s2) || !(area <= a0 * s2)) return false;
+    return true;
+}
+
+// integer box (as doubles: a candidate may lie anywhere) of a mapped quad
+STRIP_HD inline void quad_box(const double *qx, const double *qy, double *b)
+{
+    double x0 = qx[0], x1 = qx[0], y0 = qy[0], y1 = qy[0];
+    for (int i = 1; i < 4; ++i) {
+        x0 = qx[i] < x0 ? qx[i] : x0; x1 = qx[i] > x1 ? qx[i] : x1;
+        y0 = qy[i] < y0 ? qy[i] : y0; y1 = qy[i] > y1 ? qy[i] : y1;
+    }
+    b[0] = floor(x0); b[1] = floor(y0); b[2] = ceil(x1); b[3] = ceil(y1);
+}
+
+STRIP_HD inline int32_t clampi(int32_t v, int32_t lo, int32_t hi) { return v < lo ? lo : (v > hi ? hi : v); }
+
+// The chain: sequential over the frames.  H [n][9], ratio [n] (entry 0 of both is not read: frame 0 starts segment 0).
+// `fb` is scratch of [n][4] doubles (each frame's box on its segment's plane, until the segment closes).
+STRIP_HD inline void chain(const ChainParams &P, const double *H, const float *ratio, int32_t n, const ChainOut &o, double *fb)
+{
+    const double I9[9] = {1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 1.0};
+    int32_t nseg = 0, first = 0;
+    double sb[4] = {0.0, 0.0, 0.0, 0.0};         // the open segment's box
+    double Gp[9];
+    auto close = [&](int32_t end) {
+        uwip_strip_segment &s = o.segs[nseg];
+        s.first = first; s.count = end - first;
+        s.x0 = (int32_t)sb[0]; s.y0 = (int32_t)sb[1];
+        s.cols = (int32_t)(sb[2] - sb[0]) + 1; s.rows = (int32_t)(sb[3] - sb[1]) + 1;
+        s.reserved[0] = s.reserved[1] = 0;
+        for (int32_t k = first; k < end; ++k) {
+            o.seg[k] = nseg;
+            o.box[4 * k + 0] = clampi((int32_t)fb[4 * k + 0] - 1 - s.x0, 0, s.cols - 1);
+            o.box[4 * k + 1] = clampi((int32_t)fb[4 * k + 1] - 1 - s.y0, 0, s.rows - 1);
+            o.box[4 * k + 2] = clampi((int32_t)fb[4 * k + 2] + 1 - s.x0, 0, s.cols - 1);
+            o.box[4 * k + 3] = clampi((int32_t)fb[4 * k + 3] + 1 - s.y0, 0, s.rows - 1);
+        }
+        ++nseg;
+    };
+    for (int32_t k = 0; k < n; ++k) {
+        double G[9], qx[4], qy[4], b[4], nb[4];
+        bool joined = false;
+        if (k > first && ratio[k] != -2.0f) {                        // rule 1
+            const double *Hk = H + 9 * (size_t)k;
+            double M[9];
+            for (int i = 0; i < 3; ++i)
+                for (int j = 0; j < 3; ++j)
+                    M[3 * i + j] = ((Gp[3 * i] * Hk[j]) + (Gp[3 * i + 1] * Hk[3 + j])) + (Gp[3 * i + 2] * Hk[6 + j]);
+            for (int i = 0; i < 9; ++i) G[i] = M[i] / M[8];
+            if (quad_ok(P, G, qx, qy)) {                             // rules 2-4
+                quad_box(qx, qy, b);
+                nb[0] = b[0] < sb[0] ? b[0] : sb[0]; nb[1] = b[1] < sb[1] ? b[1] : sb[1];
+                nb[2] = b[2] > sb[2] ? b[2] : sb[2]; nb[3] = b[3] > sb[3] ? b[3] : sb[3];
+                joined = ((nb[2] - nb[0]) + 1.0 <= (double)P.max_cols) && ((nb[3] - nb[1]) + 1.0 <= (double)P.max_rows);   // rule 5
+            }
+        }
+        if (!joined) {
+            if (k > first) close(k);
+            first = k;
+            for (int i = 0; i < 9; ++i) G[i] = I9[i];
+            b[0] = 0.0; b[1] = 0.0; b[2] = (double)(P.w - 1); b[3] = (double)(P.h - 1);
+            for (int i = 0; i < 4; ++i) nb[i] = b[i];
+        }
+        for (int i = 0; i < 4; ++i) { sb[i] = nb[i]; fb[4 * (size_t)k + i] = b[i]; }
+        for (int i = 0; i < 9; ++i) { Gp[i] = G[i]; o.G[9 * (size_t)k + i] = G[i]; }
+        adjugate_signed(G, o.Ginv + 9 * (size_t)k);
+    }
+    if (n > 0) close(n);
+    *o.nseg = nseg;
+}
+
+// ---- the sample: canvas pixel -> source taps --------------------------------------------------------------------------
+struct Tap {
+    int32_t x, y, x1, y1;                 // the four taps' columns and rows
+    int32_t fx, fy;                       // 5-bit fractions
+    int32_t q;                            // feather weight: 1 + distance of the nearest pixel to the frame's border
+};
+
+// plane point (px, py) under A = Ginv of a w x h frame; false = not covered
+STRIP_HD inline bool sample(const double *A, double px, double py, int32_t w, int32_t h, Tap &t)
+{
+    const double d = ((A[6] * px) + (A[7] * py)) + A[8];
+    if (!(d > 0.0)) return false;
+    const double u = (((A[0] * px) + (A[1] * py)) + A[2]) / d;
+    const double v = (((A[3] * px) + (A[4] * py)) + A[5]) / d;
+    if (!(fabs(u) < 1048576.0) || !(fabs(v) < 1048576.0)) return false;
+    const int32_t U = (int32_t)floor((u * 32.0) + 0.5), V = (int32_t)floor((v * 32.0) + 0.5);
+    if (U < 0 || U > 32 * (w - 1) || V < 0 || V > 32 * (h - 1)) return false;
+    t.x = U >> 5; t.fx = U & 31; t.x1 = t.x + 1 < w - 1 ? t.x + 1 : w - 1;
+    t.y = V >> 5; t.fy = V & 31; t.y1 = t.y + 1 < h - 1 ? t.y + 1 : h - 1;
+    const int32_t xn = (U + 16) >> 5, yn = (V + 16) >> 5;
+    int32_t m = xn < w - 1 - xn ? xn : w - 1 - xn;
+    m = yn < m ? yn : m;
+    m = h - 1 - yn < m ? h - 1 - yn : m;
+    t.q = 1 + m;
+    return true;
+}
+
+// P = sum of the four taps times their 10-bit weights, 0 .. 255 * 1024
+STRIP_HD inline int32_t bilinear(const Tap &t, int32_t p00, int32_t p10, int32_t p01, int32_t p11)
+{
+    return (32 - t.fx) * (32 - t.fy) * p00 + t.fx * (32 - t.fy) * p10 + (32 - t.fx) * t.fy * p01 + t.fx * t.fy * p11;
+}
+
+}  // namespace uwip_sm

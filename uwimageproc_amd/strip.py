@@ -1,0 +1,132 @@
+"""The strip mosaic over the C ABI (include/uwip.h, "strip mosaic"): the key frames main.cpp:368-381 writes, chained by the
+homographies of videostrip.cpp:270 and rendered into one canvas per segment.  No compute here: ``Strip`` owns a
+``uwip_strip`` and hands torch tensors to it."""
+from __future__ import annotations
+
+import ctypes as C
+from typing import List, NamedTuple, Optional
+
+import numpy as np
+
+from ._native import UWIP_OK, Context, StripConfig, StripSegment, UwipError, batch_of
+
+MODES = {"feather": 0, "first": 1, "last": 2}          # UWIP_STRIP_FEATHER / FIRST / LAST
+
+
+class Segment(NamedTuple):
+    """uwip_strip_segment: frames first..first + count - 1 on a rows x cols canvas whose pixel (0, 0) is the plane point
+    (x0, y0) of the segment's first frame."""
+    first: int
+    count: int
+    x0: int
+    y0: int
+    rows: int
+    cols: int
+
+
+class Strip:
+    """``Strip(ctx, rows, cols, batch=..., max_frames=...)``: frames of rows x cols BGR, at most ``batch`` per ``add`` and
+    ``max_frames`` in all.  Further keywords are fields of uwip_strip_config (max_canvas_rows, max_canvas_cols, max_scale,
+    detect_flags, match_flags, seed, videoWidth, videoHeight)."""
+
+    def __init__(self, ctx: Context, rows: int, cols: int, batch: int = 16, max_frames: int = 1024, **fields):
+        self.ctx, self._l = ctx, ctx._l
+        cfg = StripConfig()
+        ctx.check(self._l.uwip_strip_config_default(C.byref(cfg), int(rows), int(cols)))
+        cfg.batch, cfg.max_frames = int(batch), int(max_frames)
+        for k, v in fields.items():
+            if k not in dict(StripConfig._fields_):
+                raise TypeError(f"unknown uwip_strip_config field {k!r}")
+            setattr(cfg, k, v)
+        self.cfg = cfg
+        h = C.c_void_p()
+        ctx.call("uwip_strip_create", C.byref(cfg), C.byref(h))
+        self._h = h
+        self.segments: List[Segment] = []
+
+    def close(self):
+        if getattr(self, "_h", None):
+            # a strip is bound to its context (uwip.h: destroy it before the context).  When the context has been closed
+            # first, its handle must not be touched any more: the strip is dropped, not destroyed into freed memory
+            if getattr(self.ctx, "_h", None):
+                self._l.uwip_strip_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _check(self, rc: int):
+        if rc != UWIP_OK:
+            raise UwipError(rc, self._l.uwip_strip_last_error(self._h).decode("utf-8", "replace"))
+
+    def __len__(self) -> int:
+        n = C.c_int(0)
+        self._check(self._l.uwip_strip_count(self._h, C.byref(n)))
+        return n.value
+
+    def reset(self):
+        self._check(self._l.uwip_strip_reset(self._h))
+        self.segments = []
+
+    def add(self, frames: "torch.Tensor", H: "Optional[torch.Tensor]" = None, ratio: "Optional[torch.Tensor]" = None):
+        """frames: uint8 device tensor [n, rows, cols, 3] (any row / frame stride).  With H ([n, 9] or [n, 3, 3] float64) and
+        ratio ([n] float32) on the device nothing is detected or matched: those are appended and the frames are stored as
+        they are."""
+        import torch
+
+        b = batch_of(frames)
+        if (H is None) != (ratio is None):
+            raise ValueError("inject both H and ratio, or neither")
+        if H is not None:
+            assert H.is_cuda and H.dtype == torch.float64 and H.is_contiguous() and H.numel() == 9 * b.frames
+            assert ratio.is_cuda and ratio.dtype == torch.float32 and ratio.is_contiguous() and ratio.numel() == b.frames
+        torch.cuda.current_stream(frames.device).synchronize()
+        self._check(self._l.uwip_strip_add(self._h, C.byref(b), C.c_void_p(H.data_ptr()) if H is not None else None,
+                                           C.c_void_p(ratio.data_ptr()) if H is not None else None))
+        self.ctx.sync()          # the caller's tensors may go once this returns
+        self.segments = []
+
+    def layout(self) -> List[Segment]:
+        segs, buf, n = [], (StripSegment * 64)(), C.c_int(0)
+        while True:
+            self._check(self._l.uwip_strip_layout(self._h, buf, 64, C.byref(n)))
+            segs += [Segment(s.first, s.count, s.x0, s.y0, s.rows, s.cols) for s in buf[:n.value]]
+            if n.value < 64:
+                break
+        self.segments = segs
+        return segs
+
+    def transforms(self):
+        """After ``layout``: dict of G, Ginv [n, 9] float64, seg [n] int32, box [n, 4] int32 (numpy)."""
+        n = len(self)
+        G, Gi = np.zeros((n, 9)), np.zeros((n, 9))
+        seg, box = np.zeros(n, np.int32), np.zeros((n, 4), np.int32)
+        self._check(self._l.uwip_strip_transforms(self._h, G.ctypes.data, Gi.ctypes.data, seg.ctypes.data, box.ctypes.data))
+        return {"G": G, "Ginv": Gi, "seg": seg, "box": box}
+
+    def render(self, segment: int, mode: str = "feather", fill=(0, 0, 0), cover: bool = False, out: "Optional[torch.Tensor]" = None):
+        """One segment of the last ``layout``: a uint8 tensor [rows, cols, 3] (``out``: a tensor of that shape to render
+        into, any row stride), and with ``cover`` also the [rows, cols] count of covering frames."""
+        import torch
+
+        if not self.segments:
+            self.layout()
+        s = self.segments[segment]
+        dev = torch.device("cuda", self.ctx.device)
+        if out is None:
+            out = torch.empty((s.rows, s.cols, 3), dtype=torch.uint8, device=dev)
+        if isinstance(cover, torch.Tensor):          # the caller's plane: packed [rows, cols]
+            cov = cover
+            assert cov.is_cuda and cov.dtype == torch.uint8 and cov.is_contiguous() and tuple(cov.shape) == (s.rows, s.cols)
+            cover = True
+        else:
+            cov = torch.empty((s.rows, s.cols), dtype=torch.uint8, device=dev) if cover else None
+        b = batch_of(out)
+        f = (C.c_uint8 * 3)(*[int(v) for v in fill])
+        torch.cuda.current_stream(dev).synchronize()
+        self._check(self._l.uwip_strip_render(self._h, int(segment), MODES[mode], f, C.byref(b), C.c_void_p(cov.data_ptr()) if cover else None))
+        self.ctx.sync()
+        return (out, cov) if cover else out
