@@ -1,6 +1,7 @@
-// HIP on host threads, for the emulation harnesses (jpeg_encode_emulated.cpp, jpeg_decode_emulated.cpp): enough of the device
-// language for kernels cut out of a .hip file to compile with the host compiler and run thread for thread -- one std::thread
-// per GPU thread and a barrier for __syncthreads, workgroups one after another.  Include it before the kernels.
+// HIP on host threads, for the emulation harnesses (jpeg_encode_emulated.cpp, jpeg_decode_emulated.cpp, png_decode_emulated.cpp):
+// enough of the device language for kernels cut out of a .hip file, and for a device header included as it stands
+// (csrc/png_inflate.hpp), to compile with the host compiler and run thread for thread -- one std::thread per GPU thread and a
+// barrier for __syncthreads, workgroups one after another.  Include it before the kernels.
 #pragma once
 #include <algorithm>
 #include <barrier>

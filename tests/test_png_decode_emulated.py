@@ -2,60 +2,23 @@
 the address and undefined-behaviour sanitizers) and must return the host reader's pixels (imgio::read_png, cli/imgio.hpp,
 zlib's inflate) for every stream it reads, BAD_STREAM where it does not, and write nothing outside the frame -- through the
 segmented pass and through the serial one, which the counters tell apart."""
-import os
-import subprocess
-
 import numpy as np
 import pytest
 
 import _png_decode_streams as pd
+from _png_emu import Emu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 FILTERS = (0, 1, 2, 3, 4, "mix")
 
 
 @pytest.fixture(scope="module")
 def emu(tmp_path_factory):
-    d = tmp_path_factory.mktemp("pngd_emu")
-    src = open(os.path.join(ROOT, "uwimageproc_amd", "csrc", "png_decode.hip")).read()
-    a, end = src.index("namespace {"), "}  // namespace\n"
-    b = src.index(end)
-    open(str(d / "kernels_pngd.inc"), "w").write(src[a:b + len(end)])
-    exe = str(d / "emu")
-    subprocess.run(["g++", "-std=c++20", "-O1", "-pthread", "-w", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                    "-I", str(d), "-I", os.path.join(ROOT, "include"), "-I", os.path.join(ROOT, "cli"), "-I", os.path.join(ROOT, "tests"),
-                    "-I", os.path.join(ROOT, "uwimageproc_amd", "csrc"), os.path.join(ROOT, "tests", "png_decode_emulated.cpp"),
-                    "-o", exe, "-lz"], check=True, timeout=600)
-    count = [0]
+    e = Emu(tmp_path_factory.mktemp("pngd_emu"))
 
     def run(cases):
         """cases: [(name, stream, channels, segmented)] -> {(name, segmented): dict of the printed fields}"""
-        lines = []
-        for name, stream, ch, seg in cases:
-            p = str(d / (name + ".png"))
-            open(p, "wb").write(stream)
-            lines.append(f"{p} {seg} {ch}")
-        count[0] += 1
-        lst = str(d / f"list{count[0]}.txt")
-        open(lst, "w").write("\n".join(lines) + "\n")
-        r = subprocess.run([exe, lst], capture_output=True, text=True, timeout=1500)
-        assert r.returncode == 0, (r.stdout + r.stderr)[-3000:]
-        out = {}
-        for ln in r.stdout.splitlines():
-            w = ln.split()
-            out[(os.path.basename(w[0])[:-4], int(w[1]))] = {k: int(w[i]) for k, i in (("status", 3), ("host", 5), ("equal", 7), ("clean", 9),
-                                                                                      ("accepted", 11), ("serial", 13), ("maxdist", 15))}
-        assert len(out) == len(cases), r.stdout[-3000:]
-        return out
-
-    def own(arr, filt=-1):
-        """The library's own encoder (its serial host form) on arr [H, W, 3] BGR or [H, W, 1] grey."""
-        H, W, nc = arr.shape
-        raw, png = str(d / "own.raw"), str(d / "own.png")
-        arr.tofile(raw)
-        subprocess.run([exe, "--encode", raw, str(H), str(W), str(nc), str(filt), png], check=True, timeout=300)
-        return open(png, "rb").read()
-    run.own = own
+        return {(name, seg): v for (name, seg, _), v in e([c + (0,) for c in cases]).items()}
+    run.own = e.own
     return run
 
 

@@ -1,63 +1,19 @@
-"""CPU: the found block starts of csrc/png_decode.hip (segmented = 2) run on host threads (tests/png_decode_spec_emulated.cpp, a
+"""CPU: the found block starts of csrc/png_decode.hip (segmented = 2) run on host threads (tests/png_decode_emulated.cpp, a
 stand-alone program built with the address and undefined-behaviour sanitizers).  For foreign streams of several deflate blocks
 the pixels are the host reader's (imgio::read_png) whatever the chunk size, the serial pass is not needed, and every accepted
 chunk starts at a true block start (tests/_png_spec_streams.py walks the stream on its own); streams with nothing to find and
 a stream that carries a deflate stream inside stored blocks lose no pixel; damaged streams get the status of mode 1 and of the
 host reader."""
-import os
-import subprocess
-
 import pytest
 
 import _png_spec_streams as sp
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-FIELDS = (("status", 4), ("host", 6), ("equal", 8), ("clean", 10), ("accepted", 12), ("serial", 14))
+from _png_emu import Emu
 
 
 @pytest.fixture(scope="module")
 def emu(tmp_path_factory):
-    d = tmp_path_factory.mktemp("pngd_spec_emu")
-    src = open(os.path.join(ROOT, "uwimageproc_amd", "csrc", "png_decode.hip")).read()
-    end = "}  // namespace\n"
-    a = src.index("namespace {")
-    b = src.index(end, src.index(end) + len(end))                # both anonymous namespaces: the kernels of every mode
-    open(str(d / "kernels_pngd_spec.inc"), "w").write(src[a:b + len(end)])
-    exe = str(d / "emu")
-    subprocess.run(["g++", "-std=c++20", "-O1", "-pthread", "-w", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                    "-I", str(d), "-I", os.path.join(ROOT, "include"), "-I", os.path.join(ROOT, "cli"), "-I", os.path.join(ROOT, "tests"),
-                    "-I", os.path.join(ROOT, "uwimageproc_amd", "csrc"), os.path.join(ROOT, "tests", "png_decode_spec_emulated.cpp"),
-                    "-o", exe, "-lz"], check=True, timeout=600)
-    count = [0]
-
-    def run(cases):
-        """cases: [(name, stream, channels, segmented, chunk_bytes)] -> {(name, segmented, chunk_bytes): the printed fields}"""
-        lines = []
-        for name, stream, ch, seg, cb in cases:
-            p = str(d / (name + ".png"))
-            open(p, "wb").write(stream)
-            lines.append(f"{p} {seg} {ch} {cb}")
-        # the emulation waits at barriers most of the time: four processes side by side, each with a share of the list
-        procs = []
-        for i in range(4):
-            count[0] += 1
-            lst = str(d / f"list{count[0]}.txt")
-            open(lst, "w").write("\n".join(lines[i::4]) + "\n")
-            procs.append(subprocess.Popen([exe, lst], stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True))
-        stdout = ""
-        for pr in procs:
-            o, e = pr.communicate(timeout=1500)
-            assert pr.returncode == 0, (o + e)[-3000:]
-            stdout += o
-        out = {}
-        for ln in stdout.splitlines():
-            w = ln.split()
-            v = {k: int(w[i]) for k, i in FIELDS}
-            v["starts"] = [int(x) for x in w[17:17 + int(w[16])]]
-            out[(os.path.basename(w[0])[:-4], int(w[1]), int(w[2]))] = v
-        assert len(out) == len(cases), stdout[-3000:]
-        return out
-    return run
+    """cases: [(name, stream, channels, segmented, chunk_bytes)] -> {(name, segmented, chunk_bytes): the printed fields}"""
+    return Emu(tmp_path_factory.mktemp("pngd_spec_emu"))
 
 
 @pytest.fixture(scope="module")

@@ -1,4 +1,4 @@
-// The arithmetic of inflate (RFC 1951) that is not parallel structure, written ONCE for the device kernels of png_decode.hip,
+// The arithmetic of inflate (RFC 1951) that is not parallel structure, written ONCE for the device loop of png_inflate.hpp,
 // the host parse (png_parse.hpp) and the emulation harness: the zlib header rule, the length / distance bases and extra bits,
 // the acceptance rules zlib's inflate_table applies to a set of code lengths, the canonical first codes, the look-up entry of
 // a code, the slow path for the codes the look-up table does not hold, and the fixed code.  The code-length order, the bit

@@ -3,13 +3,9 @@
 // exactly where the host reader returns true and the size fits.  The chunk walk, the IHDR rules and the zlib header are checked
 // on the host (png_parse.hpp, the host reader's walk); the IDAT payloads and one descriptor per frame and segment are uploaded.
 // The stages, all on the context's stream, none waits for the host:
-//   k_pngd_inflate  one wavefront per segment.  The symbol decode is wave-uniform and serial in the bit stream: every lane
-//                   decodes the same tokens, up to 64 per round, lane i keeps token i in LDS with its output offset (the running
-//                   sum of the token lengths).  Then all lanes write the round: literals by their lanes, matches one after the
-//                   other with the lanes across their bytes (distance < length: a period of `distance`).  A dynamic block's
-//                   tables are built by the lanes into LDS: a direct look-up table for the short codes, first code / count /
-//                   sorted symbols for the rest.  Stored blocks are a copy by all lanes.  Inflated bytes go to the frame's
-//                   workspace; back references read from there.
+//   k_pngd_inflate  one wavefront per segment runs the one inflate loop of png_inflate.hpp (inflate_run: wave-uniform symbol
+//                   decode, rounds of up to 64 tokens through LDS, then all lanes write the round) with the byte sink: inflated
+//                   bytes go to the frame's workspace; back references read from there.
 //                   Launch 0 decodes the segments the host parse proposed (cuts at IDAT boundaries behind 00 00 FF FF; segment
 //                   i assumed to start at inflated offset i * 32768); launch 1, one wavefront per frame, accepts a frame all of
 //                   whose segments report success and decodes every other frame again from its first byte.
@@ -21,13 +17,11 @@
 //                   lane L has row r0 + L and is one pixel behind lane L - 1, whose last result (through LDS) is "up", whose
 //                   result before that "upper left"; the band's first row reads the row above from memory;
 //   k_pngd_color    one thread per pixel: the type byte and alpha dropped, RGB -> BGR or grey replicated, the caller's layout.
-// What bounds the inflate loop on untrusted bytes: the bit position may not pass the segment's length (bits behind it read as
-// zeros without a load, and the first step that passes it ends the segment); every store is checked against the segment's
-// window before its token is taken; table indices are masked, or below a symbol count by construction; a round consumes at
-// least one bit or ends the segment.
+// What bounds the inflate loop on untrusted bytes, and what each of its three sinks adds, is stated once, with the loop, in
+// png_inflate.hpp; what bounds the loops around it (the search, the chain walk, the marker passes) further down.
 #include "uwip_internal.hpp"
 #include "device_utils.hpp"
-#include "inflate_core.hpp"
+#include "png_inflate.hpp"
 #include "png_parse.hpp"
 #include <cstring>
 
@@ -37,8 +31,6 @@ using namespace uwip_inflate;
 using uwip_png::kAdlerMod;
 using uwip_png::kChunk;
 
-constexpr int kLLBits = 10, kDBits = 8, kCLBits = 7;     // look-up widths: literal/length, distance, code length codes
-constexpr int kRound = 64;                               // tokens per round: one per lane
 constexpr int kBand = 64;                                // rows per pass of the unfilter: one per lane
 constexpr int kPngBad = -1;                              // UWIP_PNG_BAD_STREAM
 
@@ -80,113 +72,6 @@ struct PBufs {
 };
 
 __device__ __forceinline__ uint32_t frame_total(const PGeoD &g, int spp) { return (uint32_t)g.rows * (1u + (uint32_t)g.cols * (uint32_t)spp); }
-
-// 32 bits of the segment from bit p on, least significant first; bits at or past its last byte are zeros (no load there).
-// The second word may lie behind the segment: the buffer is 16 bytes longer than its last stream.
-__device__ __forceinline__ uint32_t peek32(const uint8_t *src, uint32_t a0, uint32_t len, uint32_t p)
-{
-    const uint32_t by = p >> 3;
-    if (by >= len) return 0u;
-    const uint32_t a = a0 + by;
-    const uint32_t *w = reinterpret_cast<const uint32_t *>(src) + (a >> 2);
-    const uint64_t x = (uint64_t)w[0] | ((uint64_t)w[1] << 32);
-    uint32_t v = (uint32_t)(x >> ((a & 3u) * 8u + (p & 7u)));
-    const uint32_t rem = len * 8u - p;                       // >= 1
-    if (rem < 32u) v &= (1u << rem) - 1u;
-    return v;
-}
-
-struct Tables {
-    uint16_t ll[1 << kLLBits], d[1 << kDBits], cl[1 << kCLBits];
-    uint16_t ll_sorted[kFixedLL], d_sorted[kFixedDist], cl_sorted[uwip_png::kNumCL];
-    CodeSet ll_set, d_set, cl_set;
-    uint8_t lens[kFixedLL + kFixedDist], cl_lens[uwip_png::kNumCL + 1];
-    uint16_t tlen[kRound], tval[kRound];                     // a round's tokens: length (1: a literal), byte or distance
-    uint32_t tout[kRound];                                   // where each goes, from the segment's first byte
-    uint32_t bad;
-};
-
-// The lanes build the decoding tables of n code lengths (each 0..15): false where zlib refuses the set.
-__device__ bool build_table(const uint8_t *lens, int n, int kind, int lutbits, uint16_t *lut, uint16_t *sorted, CodeSet &c)
-{
-    const int lane = (int)threadIdx.x;
-    if (lane < 16) c.cnt[lane] = 0u;
-    for (int i = lane; i < (1 << lutbits); i += 64) lut[i] = 0;
-    __syncthreads();
-    for (int i = lane; i < n; i += 64) if (lens[i]) atomicAdd(&c.cnt[lens[i] & 15], 1u);
-    __syncthreads();
-    if (!code_set_accepted(c.cnt, kind)) return false;       // the same answer in every lane
-    if (lane == 0) code_set_first(c);
-    __syncthreads();
-    if (lane >= 1 && lane <= kMaxBits && c.cnt[lane]) {      // lane l deals out the codes of length l in symbol order
-        const uint32_t l = (uint32_t)lane;
-        uint32_t code = c.first[l], at = c.off[l];
-        for (int s = 0; s < n; ++s) {
-            if (lens[s] != l) continue;
-            sorted[at++] = (uint16_t)s;                      // at < off[l] + cnt[l] <= n
-            if ((int)l <= lutbits)
-                for (uint32_t k = rev_bits(code, (int)l); k < (1u << lutbits); k += 1u << l) lut[k] = lut_entry((uint32_t)s, l);
-            ++code;
-        }
-    }
-    __syncthreads();
-    return true;
-}
-
-__device__ __forceinline__ bool decode_sym(const uint16_t *lut, int lutbits, const CodeSet &c, const uint16_t *sorted, uint32_t v,
-                                           uint32_t &len, uint32_t &sym)
-{
-    const uint32_t e = lut[v & ((1u << lutbits) - 1u)];
-    if (e) { len = e >> 12; sym = e & 0xFFFu; return true; }
-    return decode_slow(c, sorted, lutbits, v, len, sym);
-}
-
-// a dynamic block's header from bit pos on: the code lengths into T.lens and the two tables; false: zlib refuses it (or the
-// segment ends inside it)
-__device__ bool dynamic_header(Tables &T, const uint8_t *src, uint32_t a0, uint32_t len, uint32_t &pos)
-{
-    const uint32_t lane = threadIdx.x, lenbits = len * 8u;
-    uint32_t v = peek32(src, a0, len, pos);
-    const uint32_t nlen = (v & 31u) + 257u, nd = ((v >> 5) & 31u) + 1u, nc = ((v >> 10) & 15u) + 4u;
-    pos += 14u;
-    if (pos > lenbits || nlen > (uint32_t)kMaxLL || nd > (uint32_t)kMaxDist) return false;
-    if (lane < (uint32_t)uwip_png::kNumCL) T.cl_lens[lane] = 0;
-    __syncthreads();
-    for (uint32_t i = 0; i < nc; ++i) {                       // nc <= 19
-        const uint32_t val = peek32(src, a0, len, pos) & 7u;
-        pos += 3u;
-        if (lane == 0) T.cl_lens[cl_order((int)i)] = (uint8_t)val;
-    }
-    if (pos > lenbits) return false;
-    __syncthreads();
-    if (!build_table(T.cl_lens, uwip_png::kNumCL, kCodes, kCLBits, T.cl, T.cl_sorted, T.cl_set)) return false;
-    const uint32_t want = nlen + nd;                          // <= 316
-    uint32_t have = 0, prev = 0;
-    while (have < want) {
-        v = peek32(src, a0, len, pos);
-        const uint32_t e = T.cl[v & ((1u << kCLBits) - 1u)];  // every code of this set has at most 7 bits
-        if (!e) return false;
-        const uint32_t l = e >> 12, sym = e & 0xFFFu;
-        pos += l;
-        if (sym < 16u) {
-            if (lane == 0) T.lens[have] = (uint8_t)sym;
-            prev = sym; ++have;
-        } else {
-            uint32_t rep, val = 0;
-            if (sym == 16u) { if (have == 0u) return false; rep = 3u + ((v >> l) & 3u); pos += 2u; val = prev; }
-            else if (sym == 17u) { rep = 3u + ((v >> l) & 7u); pos += 3u; }
-            else { rep = 11u + ((v >> l) & 127u); pos += 7u; }
-            if (have + rep > want) return false;
-            for (uint32_t j = lane; j < rep; j += 64u) T.lens[have + j] = (uint8_t)val;
-            have += rep; prev = val;
-        }
-        if (pos > lenbits) return false;
-    }
-    __syncthreads();
-    if (T.lens[256] == 0) return false;                       // no end-of-block code
-    if (!build_table(T.lens, (int)nlen, kLens, kLLBits, T.ll, T.ll_sorted, T.ll_set)) return false;
-    return build_table(T.lens + nlen, (int)nd, kDists, kDBits, T.d, T.d_sorted, T.d_set);
-}
 
 // pass 0: block s is segment s.  pass 1: block f is frame f -- accepted from its segments, or decoded again as a whole.
 __global__ __launch_bounds__(64) void k_pngd_inflate(PBufs B, PGeoD g, int pass)
@@ -249,107 +134,14 @@ __global__ __launch_bounds__(64) void k_pngd_inflate(PBufs B, PGeoD g, int pass)
         out = B.ws + (size_t)f * g.ws_stride;
         lastseg = true;
     }
-    const uint8_t *src = B.src;
+    // A segment that is not the last reports success only if it ended exactly at its input's last bit, behind an empty stored
+    // block that was not final; the last segment, or the whole stream, only if it ended with the final block.  Both only with
+    // exactly their window produced (and ByteSink: no match reached before the segment's own first byte).
     const uint32_t lenbits = len * 8u;
-    uint32_t pos = 0, o = 0, maxd = 0, adler_pos = 0;
-    bool fail = false, done = false, in_block = false, final_blk = false, last_empty = false;
-    while (!done && !fail) {
-        bool block_end = false;
-        if (!in_block) {
-            uint32_t v = peek32(src, a0, len, pos);
-            final_blk = v & 1u;
-            const uint32_t type = (v >> 1) & 3u;
-            pos += 3u;
-            if (pos > lenbits) { fail = true; break; }
-            if (type == 0u) {
-                pos = (pos + 7u) & ~7u;
-                if (pos + 32u > lenbits) { fail = true; break; }
-                v = peek32(src, a0, len, pos);
-                const uint32_t L = v & 0xFFFFu;
-                pos += 32u;
-                const uint32_t by = pos >> 3;
-                if ((L ^ 0xFFFFu) != (v >> 16) || L > len - by || L > win - o) { fail = true; break; }
-                for (uint32_t j = lane; j < L; j += 64u) out[o + j] = src[a0 + by + j];
-                o += L; pos += L * 8u;
-                __syncthreads();
-                last_empty = L == 0u;
-                block_end = true;
-            } else if (type == 1u) {
-                for (uint32_t i = lane; i < (uint32_t)(kFixedLL + kFixedDist); i += 64u) T.lens[i] = (uint8_t)fixed_len((int)i);
-                __syncthreads();
-                build_table(T.lens, kFixedLL, kLens, kLLBits, T.ll, T.ll_sorted, T.ll_set);
-                build_table(T.lens + kFixedLL, kFixedDist, kDists, kDBits, T.d, T.d_sorted, T.d_set);
-                in_block = true;
-            } else if (type == 2u) {
-                if (!dynamic_header(T, src, a0, len, pos)) { fail = true; break; }
-                in_block = true;
-            } else { fail = true; break; }
-        } else {
-            // a round: up to 64 tokens, every lane decodes them all and keeps its own
-            uint32_t ntok = 0, o_r = o;
-            bool eob = false;
-            while (ntok < (uint32_t)kRound) {
-                uint32_t v = peek32(src, a0, len, pos), l, sym;
-                if (!decode_sym(T.ll, kLLBits, T.ll_set, T.ll_sorted, v, l, sym)) { fail = true; break; }
-                pos += l;
-                if (sym < 256u) {
-                    if (o_r >= win) { fail = true; break; }
-                    if (lane == ntok) { T.tlen[lane] = 1; T.tval[lane] = (uint16_t)sym; T.tout[lane] = o_r; }
-                    ++ntok; ++o_r;
-                } else if (sym == 256u) { eob = true; break; }
-                else {
-                    if (sym >= (uint32_t)kMaxLL) { fail = true; break; }
-                    const uint32_t idx = sym - 257u, eb = length_extra(idx);
-                    const uint32_t mlen = length_base(idx) + ((v >> l) & ((1u << eb) - 1u));      // l + eb <= 20 bits of v
-                    pos += eb;
-                    v = peek32(src, a0, len, pos);
-                    uint32_t l2, dsym;
-                    if (!decode_sym(T.d, kDBits, T.d_set, T.d_sorted, v, l2, dsym) || dsym >= (uint32_t)kMaxDist) { fail = true; break; }
-                    const uint32_t de = dist_extra(dsym), dist = dist_base(dsym) + ((v >> l2) & ((1u << de) - 1u));   // l2 + de <= 28
-                    pos += l2 + de;
-                    // a distance beyond the segment's own bytes: before the stream (bad), or into another segment's window
-                    if (dist > o_r || mlen > win - o_r) { fail = true; break; }
-                    maxd = max(maxd, dist);
-                    if (lane == ntok) { T.tlen[lane] = (uint16_t)mlen; T.tval[lane] = (uint16_t)dist; T.tout[lane] = o_r; }
-                    ++ntok; o_r += mlen;
-                }
-                if (pos > lenbits) { fail = true; break; }
-            }
-            if (pos > lenbits) fail = true;
-            if (fail) break;
-            __syncthreads();
-            // the round's bytes: literals first, then the matches in order; a match whose source may hold bytes of a match
-            // written since the last barrier waits for them
-            if (lane < ntok && T.tlen[lane] == 1) out[T.tout[lane]] = (uint8_t)T.tval[lane];
-            __syncthreads();
-            uint32_t dirty = 0xFFFFFFFFu;
-            for (uint32_t i = 0; i < ntok; ++i) {
-                const uint32_t ml = T.tlen[i];
-                if (ml == 1u) continue;
-                const uint32_t dist = T.tval[i], to = T.tout[i], s0 = to - dist;
-                if (s0 + min(ml, dist) > dirty) { __syncthreads(); dirty = 0xFFFFFFFFu; }
-                for (uint32_t j = lane; j < ml; j += 64u) out[to + j] = out[s0 + (dist >= ml ? j : j % dist)];
-                dirty = min(dirty, to);
-            }
-            __syncthreads();
-            o = o_r;
-            if (eob) { block_end = true; in_block = false; last_empty = false; }
-        }
-        if (block_end) {
-            if (final_blk) {
-                pos = (pos + 7u) & ~7u;
-                adler_pos = pos >> 3;
-                if (!lastseg || adler_pos + 4u > len) fail = true;            // the Adler-32 follows the last block
-                done = true;
-            } else if (!lastseg && pos == lenbits) {                          // the segment's input ends here
-                if (!last_empty) fail = true;
-                done = true;
-            }
-        }
-    }
-    const bool ok = !fail && o == win;
+    const InflateRun r = inflate_run(T, B.src, a0, len, 0u, lastseg ? kNone : lenbits, ByteSink{out}, win);
+    const bool ok = r.ok && r.nbytes == win && (lastseg ? r.final_blk : !r.final_blk && r.last_empty && r.end == lenbits);
     if (lane == 0) {
-        B.res[rslot] = PRes{ok ? 1u : 0u, a0 - B.fr[f].zoff + adler_pos, maxd, 0u};
+        B.res[rslot] = PRes{ok ? 1u : 0u, a0 - B.fr[f].zoff + r.adler_pos, r.maxdist, 0u};
         if (pass == 0) { if (ok) atomicAdd(&B.counts[0], 1ull); }
         else B.status[f] = ok ? 0 : kPngBad;
     }
@@ -444,33 +236,6 @@ __global__ __launch_bounds__(256) void k_pngd_color(PBufs B, PGeoD g, uint8_t *o
     else { p[0] = s[2]; p[1] = s[1]; p[2] = s[0]; }
 }
 
-// ---- the host side ----------------------------------------------------------------------------------------------------------
-struct PPlan {
-    size_t src_bytes = 0, nseg = 0;
-    bool too_large = false;
-};
-
-// the per-frame workspace comes from the batch's geometry at four samples per pixel, never from an IHDR
-size_t ws_bytes(int rows, int cols) { return (((size_t)rows * ((size_t)cols * 4 + 1)) + 15) & ~(size_t)15; }
-
-// a frame's descriptor and segments from its parse; segmented: one segment per proposed cut and one behind the last
-void plan_frame(PFrame &d, const uwip_pngd::Parsed &p, int rows, int cols, int segmented, std::vector<PSeg> &segs, int f, PPlan &pl)
-{
-    d.zoff = (uint32_t)pl.src_bytes; d.zlen = (uint32_t)p.zlen;
-    pl.src_bytes += (p.zlen + 31) & ~(size_t)15;
-    d.seg0 = (uint32_t)segs.size(); d.nseg = 0;
-    if (segmented == 1 || (segmented == 2 && !p.cuts.empty())) {      // 2: a stream without cuts is left to the found block starts
-        size_t at = 2;
-        uint32_t i = 0;
-        for (size_t c : p.cuts) { segs.push_back(PSeg{(uint32_t)f, i++, (uint32_t)at, (uint32_t)(c - at)}); at = c; }
-        segs.push_back(PSeg{(uint32_t)f, i++, (uint32_t)at, (uint32_t)(p.zlen - at)});
-        d.nseg = i;
-    }
-    if (pl.src_bytes >= ((size_t)1 << 31)) pl.too_large = true;
-}
-
-}  // namespace
-
 // ---- found block starts (segmented = 2) ------------------------------------------------------------------------
 // A stream without flush points is cut into chunks of chunk_bytes compressed bytes.  Kernels, each one launch, no workgroup
 // waits for another -- the order between chunks comes from the kernel boundaries alone:
@@ -478,135 +243,27 @@ void plan_frame(PFrame &d, const uwip_pngd::Parsed &p, int rows, int cols, int s
 //   k_pngs_measure  one wavefront per (chunk, frame).  Chunk 0 starts behind the zlib header.  Every other chunk looks for
 //                   the first bit of its range that passes as the start of a dynamic block: the lanes screen kScreen x 64
 //                   positions a round in registers (dynamic_start_plausible), the first that passes gets dynamic_header, and
-//                   from there the wavefront decodes lengths only -- no store, no window -- through whole blocks up to the
+//                   from there the wavefront decodes lengths only (inflate_run without a sink) through whole blocks up to the
 //                   first block boundary at or behind the end of its range.  A decode that fails discards the candidate and
 //                   the search goes on one bit later.  The record: start bit, end bit, bytes produced.
 //                   As a repair pass (one wavefront per frame) it measures from the accepted chain's end, any block type;
 //   k_pngs_verify   one thread per frame walks the chain: the chunk whose range holds the chain's end is accepted iff it
 //                   starts exactly there, and gets the chain's byte count as its output offset; otherwise a repair pass is
 //                   asked for (kRepairs of them per call), and the frame is given up when they are spent;
-//   k_pngs_write    one wavefront per accepted chunk decodes again, as k_pngd_inflate does, into 16-bit elements;
+//   k_pngs_write    one wavefront per accepted chunk decodes again, the same loop with the element sink: 16-bit elements;
 //   k_pngs_window   one workgroup per frame, the chunks in order: the markers in a chunk's last 32 768 elements become bytes;
 //   k_pngs_resolve  one workgroup per accepted chunk: elements to bytes in the frame's workspace.
-// What bounds the loops on untrusted bytes: the search position only grows and ends at the chunk's range, and at most
-// kMaxTries candidates of a chunk get the full decode; a decode step consumes at least one bit or ends the run, and no bit
-// position passes the stream's length by more than one token (peek32 reads zeros there without a load); a measured run may
-// not produce more than the frame's bytes; verify accepts a chunk only inside the frame (out_off + nbytes <= total, total <=
-// ws_stride), each acceptance moves to a later range, so its loop takes at most nchunks steps; every store of k_pngs_write is
-// checked against the chunk's measured length before its token is taken; k_pngs_window and k_pngs_resolve form a source index
-// only where k + 1 <= out_off, and their element loops run over measured lengths; table indices as in k_pngd_inflate.
-namespace {
-
-constexpr uint32_t kNone = 0xFFFFFFFFu;
+// What bounds the loops around inflate_run on untrusted bytes: the search position only grows and ends at the chunk's range,
+// and at most kMaxTries candidates of a chunk get the full decode; a measured run may not produce more than the frame's bytes
+// (its window); verify accepts a chunk only inside the frame (out_off + nbytes <= total, total <= ws_stride), each acceptance
+// moves to a later range, so its loop takes at most nchunks steps; the window of k_pngs_write is the chunk's measured length;
+// k_pngs_window and k_pngs_resolve form a source index only where k + 1 <= out_off, and their element loops run over measured
+// lengths.
 constexpr uint32_t kChunkValid = 1u, kChunkFinal = 2u;
-constexpr uint32_t kMarker = 0x8000u;
 constexpr int kRepairs = 4;                              // repair passes per call
 constexpr int kScreen = 4;                               // bit positions a lane screens per round
 constexpr int kMaxTries = 256;                           // candidates of one chunk that get the full decode
 constexpr uint32_t kSpecChunkDefault = 16384;            // chunk_bytes 0
-
-struct SpecRun { uint32_t end, nbytes, adler_pos; bool ok, final_blk; };
-
-// Whole blocks from the block header at bit `pos` up to the first block boundary at or behind bit `stop`, or through the final
-// block.  out == nullptr: lengths only, at most `win` bytes.  Otherwise the 16-bit elements of out[0, win): a byte, or kMarker | k
-// for "the byte k + 1 before out[0]" -- a match copies elements, so a reference into the bytes before the chunk is handed on --
-// and a distance that reaches before the stream's first byte (abs0 bytes lie before out[0]) fails the run.
-__device__ SpecRun spec_run(Tables &T, const uint8_t *src, uint32_t a0, uint32_t len, uint32_t pos, uint32_t stop, bool first_dynamic,
-                            uint16_t *out, uint32_t win, uint32_t abs0)
-{
-    const uint32_t lane = threadIdx.x, lenbits = len * 8u;
-    SpecRun r{0u, 0u, 0u, false, false};
-    uint32_t o = 0;
-    for (bool first = true;; first = false) {
-        uint32_t v = peek32(src, a0, len, pos);
-        const bool final_blk = v & 1u;
-        const uint32_t type = (v >> 1) & 3u;
-        pos += 3u;
-        if (pos > lenbits || type == 3u || (first && first_dynamic && type != 2u)) return r;
-        if (type == 0u) {
-            pos = (pos + 7u) & ~7u;
-            if (pos + 32u > lenbits) return r;
-            v = peek32(src, a0, len, pos);
-            const uint32_t L = v & 0xFFFFu;
-            pos += 32u;
-            const uint32_t by = pos >> 3;
-            if ((L ^ 0xFFFFu) != (v >> 16) || L > len - by || L > win - o) return r;
-            if (out) {
-                for (uint32_t j = lane; j < L; j += 64u) out[o + j] = src[a0 + by + j];
-                __syncthreads();
-            }
-            o += L; pos += L * 8u;
-        } else {
-            if (type == 1u) {
-                for (uint32_t i = lane; i < (uint32_t)(kFixedLL + kFixedDist); i += 64u) T.lens[i] = (uint8_t)fixed_len((int)i);
-                __syncthreads();
-                build_table(T.lens, kFixedLL, kLens, kLLBits, T.ll, T.ll_sorted, T.ll_set);
-                build_table(T.lens + kFixedLL, kFixedDist, kDists, kDBits, T.d, T.d_sorted, T.d_set);
-            } else if (!dynamic_header(T, src, a0, len, pos)) return r;
-            for (bool eob = false; !eob;) {
-                // a round as in k_pngd_inflate: up to 64 tokens when they are stored, the whole block when they are not
-                uint32_t ntok = 0, o_r = o;
-                while (!out || ntok < (uint32_t)kRound) {
-                    uint32_t l, sym;
-                    v = peek32(src, a0, len, pos);
-                    if (!decode_sym(T.ll, kLLBits, T.ll_set, T.ll_sorted, v, l, sym)) return r;
-                    pos += l;
-                    if (sym < 256u) {
-                        if (o_r >= win) return r;
-                        if (out && lane == ntok) { T.tlen[lane] = 1; T.tval[lane] = (uint16_t)sym; T.tout[lane] = o_r; }
-                        ++ntok; ++o_r;
-                    } else if (sym == 256u) { eob = true; break; }
-                    else {
-                        if (sym >= (uint32_t)kMaxLL) return r;
-                        const uint32_t idx = sym - 257u, eb = length_extra(idx);
-                        const uint32_t mlen = length_base(idx) + ((v >> l) & ((1u << eb) - 1u));
-                        pos += eb;
-                        v = peek32(src, a0, len, pos);
-                        uint32_t l2, dsym;
-                        if (!decode_sym(T.d, kDBits, T.d_set, T.d_sorted, v, l2, dsym) || dsym >= (uint32_t)kMaxDist) return r;
-                        const uint32_t de = dist_extra(dsym), dist = dist_base(dsym) + ((v >> l2) & ((1u << de) - 1u));   // <= 32768
-                        pos += l2 + de;
-                        if (mlen > win - o_r || (out && dist > abs0 + o_r)) return r;
-                        if (out && lane == ntok) { T.tlen[lane] = (uint16_t)mlen; T.tval[lane] = (uint16_t)(dist - 1u); T.tout[lane] = o_r; }
-                        ++ntok; o_r += mlen;
-                    }
-                    if (pos > lenbits) return r;
-                }
-                if (pos > lenbits) return r;
-                if (out) {
-                    __syncthreads();
-                    if (lane < ntok && T.tlen[lane] == 1) out[T.tout[lane]] = T.tval[lane];
-                    __syncthreads();
-                    uint32_t dirty = kNone;
-                    for (uint32_t i = 0; i < ntok; ++i) {
-                        const uint32_t ml = T.tlen[i];
-                        if (ml == 1u) continue;
-                        const uint32_t dist = (uint32_t)T.tval[i] + 1u, to = T.tout[i];
-                        const int s0 = (int)to - (int)dist;                              // before out[0]: markers, nothing is read
-                        if (dirty != kNone && s0 + (int)min(ml, dist) > (int)dirty) { __syncthreads(); dirty = kNone; }
-                        for (uint32_t j = lane; j < ml; j += 64u) {
-                            const int q = s0 + (int)(dist >= ml ? j : j % dist);         // < to; -q - 1 <= dist - 1 <= 32767
-                            out[to + j] = q >= 0 ? out[q] : (uint16_t)(kMarker | (uint32_t)(-q - 1));
-                        }
-                        dirty = min(dirty, to);
-                    }
-                    __syncthreads();
-                }
-                o = o_r;
-            }
-        }
-        if (final_blk) {
-            pos = (pos + 7u) & ~7u;
-            r.adler_pos = pos >> 3;
-            if (r.adler_pos + 4u > len) return r;                                        // the Adler-32 follows the last block
-            r.final_blk = true;
-            break;
-        }
-        if (pos >= stop) break;
-    }
-    r.ok = true; r.end = pos; r.nbytes = o;
-    return r;
-}
 
 __global__ __launch_bounds__(64) void k_pngs_begin(PBufs B)
 {
@@ -642,10 +299,10 @@ __global__ __launch_bounds__(64) void k_pngs_measure(PBufs B, PGeoD g, int repai
     const uint32_t a0 = fr.zoff + 2u, len = fr.zlen - 2u, lenbits = len * 8u, total = frame_total(g, fr.spp);
     const uint32_t hi = min((c + 1u) * B.chunk_bits, lenbits);
     const uint8_t *src = B.src;
-    SpecRun r{0u, 0u, 0u, false, false};
+    InflateRun r{0u, 0u, 0u, 0u, false, false, false};
     uint32_t start = lo;
     int tries = 0;
-    if (repair || c == 0u) r = spec_run(T, src, a0, len, lo, hi, false, nullptr, total, 0u);
+    if (repair || c == 0u) r = inflate_run(T, src, a0, len, lo, hi, LengthsOnly{}, total);
     else {
         uint32_t p = lo;
         int par = 0;
@@ -666,7 +323,7 @@ __global__ __launch_bounds__(64) void k_pngs_measure(PBufs B, PGeoD g, int repai
             par ^= 1;
             if (q == kNone) { p += 64u * (uint32_t)kScreen; continue; }
             ++tries;
-            r = spec_run(T, src, a0, len, q, hi, true, nullptr, total, 0u);
+            r = inflate_run(T, src, a0, len, q, hi, LengthsOnly{}, total);      // the screen saw BTYPE 2 at q: a dynamic block
             if (r.ok) { start = q; break; }
             p = q + 1u;
         }
@@ -721,7 +378,7 @@ __global__ __launch_bounds__(64) void k_pngs_write(PBufs B, PGeoD g)
     const PFrame fr = B.fr[f];
     const PChunk k = B.chunk[fr.chunk0 + B.order[fr.chunk0 + blockIdx.x]];
     uint16_t *out = B.sym + (size_t)f * g.ws_stride + k.out_off;
-    const SpecRun r = spec_run(T, B.src, fr.zoff + 2u, fr.zlen - 2u, k.start, k.end, false, out, k.nbytes, k.out_off);
+    const InflateRun r = inflate_run(T, B.src, fr.zoff + 2u, fr.zlen - 2u, k.start, k.end, ElemSink{out, k.out_off}, k.nbytes);
     if (!(r.ok && r.end == k.end && r.nbytes == k.nbytes) && threadIdx.x == 0) B.spec[f].ok = 0u;
 }
 
@@ -769,6 +426,31 @@ __global__ __launch_bounds__(256) void k_pngs_resolve(PBufs B, PGeoD g)
         out[e] = (uint8_t)v;
     }
     if (bad) B.spec[f].ok = 0u;
+}
+
+// ---- the host side ----------------------------------------------------------------------------------------------------------
+struct PPlan {
+    size_t src_bytes = 0, nseg = 0;
+    bool too_large = false;
+};
+
+// the per-frame workspace comes from the batch's geometry at four samples per pixel, never from an IHDR
+size_t ws_bytes(int rows, int cols) { return (((size_t)rows * ((size_t)cols * 4 + 1)) + 15) & ~(size_t)15; }
+
+// a frame's descriptor and segments from its parse; segmented: one segment per proposed cut and one behind the last
+void plan_frame(PFrame &d, const uwip_pngd::Parsed &p, int rows, int cols, int segmented, std::vector<PSeg> &segs, int f, PPlan &pl)
+{
+    d.zoff = (uint32_t)pl.src_bytes; d.zlen = (uint32_t)p.zlen;
+    pl.src_bytes += (p.zlen + 31) & ~(size_t)15;
+    d.seg0 = (uint32_t)segs.size(); d.nseg = 0;
+    if (segmented == 1 || (segmented == 2 && !p.cuts.empty())) {      // 2: a stream without cuts is left to the found block starts
+        size_t at = 2;
+        uint32_t i = 0;
+        for (size_t c : p.cuts) { segs.push_back(PSeg{(uint32_t)f, i++, (uint32_t)at, (uint32_t)(c - at)}); at = c; }
+        segs.push_back(PSeg{(uint32_t)f, i++, (uint32_t)at, (uint32_t)(p.zlen - at)});
+        d.nseg = i;
+    }
+    if (pl.src_bytes >= ((size_t)1 << 31)) pl.too_large = true;
 }
 
 // ---- the host side of the found block starts ----
