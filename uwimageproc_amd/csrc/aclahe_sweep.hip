@@ -49,28 +49,53 @@ __device__ __forceinline__ uint32_t sweep_eval(uint32_t pk, float xa1, float xa,
     return __builtin_amdgcn_cvt_pk_u8_f32(res, 0, 0u);     // RNE + clamp
 }
 
-// clip limits K0 .. K0+N-1 of one pixel: the N LUT reads go out together, their evaluations interleave
-template <int K0, int N>
-__device__ __forceinline__ void sweep_run(const uint32_t *pack_v, uint32_t *my_hist, float xa1, float xa, float ya1, float ya)
+// s_pack by grey level: limits 0 .. 15 of the group as [256 grey][4 quads][4 limits] dwords (64 B per grey level, one
+// ds_read_b128 per quad of limits), limit 16 in a [256] row of its own behind them (read only where nd == 17).
+// A ds_read_b128 is served in 16 slots of 16 B per 256-B row; unswizzled, quad q of grey v sits in slot (4v + q) mod 16, which
+// depends on v mod 4 only.  Quad q of grey v is therefore stored at quad position q ^ ((v >> 2) & 3): the slot depends on
+// v mod 16.  sweep_quad0(v) ^ q is the uint4 index of quad q (the pack stage and the reads both use it).
+constexpr int SWEEP_QUADS = (SWEEP_GROUP - 1) / 4;
+constexpr int SWEEP_ROW16 = SWEEP_QUADS * 4 * 256;          // dword offset of limit 16's row
+static_assert(SWEEP_GROUP == 4 * SWEEP_QUADS + 1 && (SWEEP_QUADS + 1) * 64 <= SWEEP_THREADS, "four quads and one row; one pack task per thread");
+__device__ __forceinline__ uint32_t sweep_quad0(uint32_t v) { return v * 4u + ((v >> 2) & 3u); }
+
+// clip limits 0 .. N-1 of one pixel from their packed tuples: the evaluations interleave
+template <int N>
+__device__ __forceinline__ void sweep_run(const uint32_t *pk, uint32_t *my_hist, float xa1, float xa, float ya1, float ya)
 {
-    uint32_t pk[N];
-#pragma unroll
-    for (int i = 0; i < N; ++i) pk[i] = pack_v[(K0 + i) * 256];
     // Limits 2j and 2j + 1 share a counter word (low / high half).  Where a pixel's two outputs agree -- neighbouring limits
     // often blend the same four LUT entries -- ONE atomic adds to both halves, and the second one runs only for the lanes that
     // differ (fewer active lanes = fewer same-bank collisions in the LDS pipe, the kernel's other limit).
-    uint32_t o[N];
+    uint32_t o[N > 0 ? N : 1];
 #pragma unroll
     for (int i = 0; i < N; ++i) o[i] = sweep_eval(pk[i], xa1, xa, ya1, ya);
-    constexpr int FIRST = K0 & 1;            // an odd first limit is the high half of a word on its own
-    if constexpr (FIRST) atomicAdd(&my_hist[(K0 >> 1) * 256 + o[0]], 65536u);
 #pragma unroll
-    for (int i = FIRST; i + 1 < N; i += 2) {
+    for (int i = 0; i + 1 < N; i += 2) {
         const bool same = o[i] == o[i + 1];
-        atomicAdd(&my_hist[((K0 + i) >> 1) * 256 + o[i]], same ? 0x10001u : 1u);
-        if (!same) atomicAdd(&my_hist[((K0 + i) >> 1) * 256 + o[i + 1]], 65536u);
+        atomicAdd(&my_hist[(i >> 1) * 256 + o[i]], same ? 0x10001u : 1u);
+        if (!same) atomicAdd(&my_hist[(i >> 1) * 256 + o[i + 1]], 65536u);
     }
-    if constexpr (((N - FIRST) & 1) != 0) atomicAdd(&my_hist[((K0 + N - 1) >> 1) * 256 + o[N - 1]], 1u);
+    if constexpr ((N & 1) != 0) atomicAdd(&my_hist[((N - 1) >> 1) * 256 + o[N - 1]], 1u);
+}
+
+// one pixel of a cell with ns = 4 NQ + R < 16: quads 0 .. NQ go out together, limits 0 .. ns-1 are counted in H and limit ns
+// (position R of quad NQ) in the tail
+template <int NQ, int R>
+__device__ __forceinline__ void sweep_pixel(const uint4 *pack4, uint32_t q0, uint32_t *my_hist, uint32_t *s_tail, uint32_t *s_g, bool g_sep,
+                                            bool g_last, float xa1, float xa, float ya1, float ya)
+{
+    constexpr int NS = 4 * NQ + R;
+    uint32_t pk[4 * (NQ + 1)];
+#pragma unroll
+    for (int i = 0; i <= NQ; ++i) {
+        const uint4 q = pack4[q0 ^ (uint32_t)i];
+        pk[4 * i] = q.x; pk[4 * i + 1] = q.y; pk[4 * i + 2] = q.z; pk[4 * i + 3] = q.w;
+    }
+    if (g_sep) atomicAdd(&s_g[sweep_eval(pk[0], xa1, xa, ya1, ya)], 65536u);
+    sweep_run<NS>(pk, my_hist, xa1, xa, ya1, ya);
+    const uint32_t o_last = sweep_eval(pk[NS], xa1, xa, ya1, ya);
+    atomicAdd(&s_tail[(NS >> 1) * 256 + o_last], (NS & 1) ? 65536u : 1u);
+    if (g_last) atomicAdd(&s_g[o_last], 65536u);
 }
 
 __global__ __launch_bounds__(SWEEP_THREADS) void k_clahe_sweep(const uint8_t *__restrict__ src, size_t step,
@@ -84,7 +109,7 @@ __global__ __launch_bounds__(SWEEP_THREADS) void k_clahe_sweep(const uint8_t *__
                                                      ClipList cl)
 {
     extern __shared__ __attribute__((aligned(16))) uint32_t s_sweep[];
-    uint32_t *s_pack = s_sweep;                                   // [SWEEP_GROUP][256]
+    uint32_t *s_pack = s_sweep;                                   // [256][SWEEP_QUADS][4] swizzled + [256] for limit 16 (sweep_quad0)
     uint32_t *s_hist = s_sweep + SWEEP_GROUP * 256;               // [SWEEP_REP][SWEEP_HROWS][256], two 16-bit counters per word
     uint32_t *s_tail = s_hist + SWEEP_REP * SWEEP_RSTRIDE;        // [SWEEP_TROWS][256], same packing
     const int tid = threadIdx.x;
@@ -125,21 +150,36 @@ __global__ __launch_bounds__(SWEEP_THREADS) void k_clahe_sweep(const uint8_t *__
         int nd = 1;
         for (int c = 1; c < SWEEP_GROUP; ++c) nd += (uint32_t)cl.clip[cg * SWEEP_GROUP + c - 1] < cellmax ? 1 : 0;
         const int ns = nd - 1;                                     // limits 0 .. ns-1 go to H, limit ns to T[ns]
-        // four grey levels per thread: one dword from each of the four tiles' LUTs, byte-transposed by v_perm into
-        // four packed entries (TL | TR << 8 | BL << 16 | BR << 24) and stored as one 16-byte LDS write; rows >= nd are
-        // never read
-        for (int idx = tid; idx < nd * 64; idx += SWEEP_THREADS) {
-            const int c = idx >> 6, v4 = idx & 63;
-            const uint32_t *Lc = reinterpret_cast<const uint32_t *>(L + (size_t)c * 256);
-            const uint32_t a = Lc[((size_t)ty1 * gx + tx1) * (SWEEP_NCL * 64) + v4];
-            const uint32_t b = Lc[((size_t)ty1 * gx + tx2) * (SWEEP_NCL * 64) + v4];
-            const uint32_t cc = Lc[((size_t)ty2 * gx + tx1) * (SWEEP_NCL * 64) + v4];
-            const uint32_t d = Lc[((size_t)ty2 * gx + tx2) * (SWEEP_NCL * 64) + v4];
-            const uint32_t t0 = __builtin_amdgcn_perm(b, a, 0x05010400u), t1 = __builtin_amdgcn_perm(b, a, 0x07030602u);
-            const uint32_t u0 = __builtin_amdgcn_perm(d, cc, 0x05010400u), u1 = __builtin_amdgcn_perm(d, cc, 0x07030602u);
-            reinterpret_cast<uint4 *>(s_pack)[idx] =
-                make_uint4(__builtin_amdgcn_perm(u0, t0, 0x05040100u), __builtin_amdgcn_perm(u0, t0, 0x07060302u),
-                           __builtin_amdgcn_perm(u1, t1, 0x05040100u), __builtin_amdgcn_perm(u1, t1, 0x07060302u));
+        // A thread takes four grey levels of one quad of limits (wave w: quad w; wave 4: limit 16 where nd == 17): per limit one
+        // dword from each of the four tiles' LUTs, byte-transposed by v_perm into four packed entries
+        // (TL | TR << 8 | BL << 16 | BR << 24), then one 16-byte LDS write per grey level.  Quads >= ceil(nd / 4) are never read.
+        {
+            const int qd = tid >> 6, v4 = tid & 63;
+            const int nq = min((nd + 3) >> 2, SWEEP_QUADS);
+            const bool row16 = qd == SWEEP_QUADS && nd == SWEEP_GROUP;
+            if (qd < nq || row16) {
+                uint32_t e[4][4] = {};                                   // [grey 4 v4 + k][limit 4 qd + j]
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    if (j > 0 && row16) break;
+                    const uint32_t *Lc = reinterpret_cast<const uint32_t *>(L + (size_t)(qd * 4 + j) * 256);
+                    const uint32_t a = Lc[((size_t)ty1 * gx + tx1) * (SWEEP_NCL * 64) + v4];
+                    const uint32_t b = Lc[((size_t)ty1 * gx + tx2) * (SWEEP_NCL * 64) + v4];
+                    const uint32_t cc = Lc[((size_t)ty2 * gx + tx1) * (SWEEP_NCL * 64) + v4];
+                    const uint32_t d = Lc[((size_t)ty2 * gx + tx2) * (SWEEP_NCL * 64) + v4];
+                    const uint32_t t0 = __builtin_amdgcn_perm(b, a, 0x05010400u), t1 = __builtin_amdgcn_perm(b, a, 0x07030602u);
+                    const uint32_t u0 = __builtin_amdgcn_perm(d, cc, 0x05010400u), u1 = __builtin_amdgcn_perm(d, cc, 0x07030602u);
+                    e[0][j] = __builtin_amdgcn_perm(u0, t0, 0x05040100u); e[1][j] = __builtin_amdgcn_perm(u0, t0, 0x07060302u);
+                    e[2][j] = __builtin_amdgcn_perm(u1, t1, 0x05040100u); e[3][j] = __builtin_amdgcn_perm(u1, t1, 0x07060302u);
+                }
+                if (row16) {
+                    reinterpret_cast<uint4 *>(s_pack + SWEEP_ROW16)[v4] = make_uint4(e[0][0], e[1][0], e[2][0], e[3][0]);
+                } else {
+#pragma unroll
+                    for (int k = 0; k < 4; ++k)
+                        reinterpret_cast<uint4 *>(s_pack)[sweep_quad0((uint32_t)(4 * v4 + k)) ^ (uint32_t)qd] = make_uint4(e[k][0], e[k][1], e[k][2], e[k][3]);
+                }
+            }
         }
         __syncthreads();
         // with rep1 the last distinct limit is the unclipped LUT itself: its output is reused for G
@@ -196,45 +236,42 @@ __global__ __launch_bounds__(SWEEP_THREADS) void k_clahe_sweep(const uint8_t *__
             const float xa = txf - floorf(txf), xa1 = 1.0f - xa;
             const float tyf = (float)y * inv_th - 0.5f;
             const float ya = tyf - floorf(tyf), ya1 = 1.0f - ya;
-            const uint32_t *pack_v = s_pack + v;
-            if (g_sep) atomicAdd(&s_g[sweep_eval(pack_v[0], xa1, xa, ya1, ya)], 65536u);
+            const uint4 *pack4 = reinterpret_cast<const uint4 *>(s_pack);
+            const uint32_t q0 = sweep_quad0(v);
             if (nd == SWEEP_GROUP) {
-                sweep_run<0, SWEEP_GROUP>(pack_v, my_hist, xa1, xa, ya1, ya);      // every clip limit has its own LUTs
+                // every clip limit has its own LUTs: four quads and limit 16's row, all into H
+                uint32_t pk[SWEEP_GROUP];
+                pk[SWEEP_GROUP - 1] = s_pack[SWEEP_ROW16 + v];
+#pragma unroll
+                for (int i = 0; i < SWEEP_QUADS; ++i) {
+                    const uint4 q = pack4[q0 ^ (uint32_t)i];
+                    pk[4 * i] = q.x; pk[4 * i + 1] = q.y; pk[4 * i + 2] = q.z; pk[4 * i + 3] = q.w;
+                }
+                if (g_sep) atomicAdd(&s_g[sweep_eval(pk[0], xa1, xa, ya1, ya)], 65536u);
+                sweep_run<SWEEP_GROUP>(pk, my_hist, xa1, xa, ya1, ya);
                 continue;
             }
-            {
-                // ns evaluations in straight-line runs of 8 / 4 / 2 / 1 (ns < 16), then the last distinct limit into the tail
-                const uint32_t pk_last = pack_v[ns * 256];
-                if (ns & 8) sweep_run<0, 8>(pack_v, my_hist, xa1, xa, ya1, ya);
-                if (ns & 4) {
-                    if (ns & 8) sweep_run<8, 4>(pack_v, my_hist, xa1, xa, ya1, ya);
-                    else sweep_run<0, 4>(pack_v, my_hist, xa1, xa, ya1, ya);
-                }
-                if (ns & 2) {
-                    switch (ns & 12) {
-                    case 0: sweep_run<0, 2>(pack_v, my_hist, xa1, xa, ya1, ya); break;
-                    case 4: sweep_run<4, 2>(pack_v, my_hist, xa1, xa, ya1, ya); break;
-                    case 8: sweep_run<8, 2>(pack_v, my_hist, xa1, xa, ya1, ya); break;
-                    default: sweep_run<12, 2>(pack_v, my_hist, xa1, xa, ya1, ya); break;
-                    }
-                }
-                if (ns & 1) {
-                    switch (ns & 14) {
-                    case 0: sweep_run<0, 1>(pack_v, my_hist, xa1, xa, ya1, ya); break;
-                    case 2: sweep_run<2, 1>(pack_v, my_hist, xa1, xa, ya1, ya); break;
-                    case 4: sweep_run<4, 1>(pack_v, my_hist, xa1, xa, ya1, ya); break;
-                    case 6: sweep_run<6, 1>(pack_v, my_hist, xa1, xa, ya1, ya); break;
-                    case 8: sweep_run<8, 1>(pack_v, my_hist, xa1, xa, ya1, ya); break;
-                    case 10: sweep_run<10, 1>(pack_v, my_hist, xa1, xa, ya1, ya); break;
-                    case 12: sweep_run<12, 1>(pack_v, my_hist, xa1, xa, ya1, ya); break;
-                    default: sweep_run<14, 1>(pack_v, my_hist, xa1, xa, ya1, ya); break;
-                    }
-                }
-                const uint32_t o_last = sweep_eval(pk_last, xa1, xa, ya1, ya);
-                atomicAdd(&s_tail[(ns >> 1) * 256 + o_last], (ns & 1) ? 65536u : 1u);
-                if (g_last) atomicAdd(&s_g[o_last], 65536u);
-                continue;
+            // ns < 16 (block-uniform): straight-line code per number of quads and position of the last distinct limit
+#define SWEEP_PIXEL(NQ, R) sweep_pixel<NQ, R>(pack4, q0, my_hist, s_tail, s_g, g_sep, g_last, xa1, xa, ya1, ya); break
+            switch (ns) {
+            case 0: SWEEP_PIXEL(0, 0);
+            case 1: SWEEP_PIXEL(0, 1);
+            case 2: SWEEP_PIXEL(0, 2);
+            case 3: SWEEP_PIXEL(0, 3);
+            case 4: SWEEP_PIXEL(1, 0);
+            case 5: SWEEP_PIXEL(1, 1);
+            case 6: SWEEP_PIXEL(1, 2);
+            case 7: SWEEP_PIXEL(1, 3);
+            case 8: SWEEP_PIXEL(2, 0);
+            case 9: SWEEP_PIXEL(2, 1);
+            case 10: SWEEP_PIXEL(2, 2);
+            case 11: SWEEP_PIXEL(2, 3);
+            case 12: SWEEP_PIXEL(3, 0);
+            case 13: SWEEP_PIXEL(3, 1);
+            case 14: SWEEP_PIXEL(3, 2);
+            default: SWEEP_PIXEL(3, 3);
             }
+#undef SWEEP_PIXEL
         }
     }
     __syncthreads();
