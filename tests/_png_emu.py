@@ -1,26 +1,20 @@
 """The emulation harness of the PNG decoder for the two test modules that drive it: tests/png_decode_emulated.cpp, a stand-alone
 program built with the address and undefined-behaviour sanitizers, runs the kernels of csrc/png_decode.hip on host threads.
 The inflate machinery (csrc/png_inflate.hpp) is included by the harness as it stands; the kernels and the host planning are cut
-out of the .hip file: its anonymous namespace."""
+out of the .hip file (tests/_emu_build.py): its first anonymous namespace, which holds the unit's host sequence as well."""
 import os
 import subprocess
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+import _emu_build as eb
+
 FIELDS = (("status", 4), ("host", 6), ("equal", 8), ("clean", 10), ("accepted", 12), ("serial", 14), ("maxdist", 16))
 
 
 class Emu:
     def __init__(self, d):
-        self.d, self.exe, self.count = d, str(d / "emu"), 0
-        src = open(os.path.join(ROOT, "uwimageproc_amd", "csrc", "png_decode.hip")).read()
-        end = "}  // namespace\n"
-        a, b = src.index("namespace {"), src.index(end)
-        assert src.count("namespace {") == 1 and src.count(end) == 1
-        open(str(d / "kernels_pngd.inc"), "w").write(src[a:b + len(end)])
-        subprocess.run(["g++", "-std=c++20", "-O1", "-pthread", "-w", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                        "-I", str(d), "-I", os.path.join(ROOT, "include"), "-I", os.path.join(ROOT, "cli"), "-I", os.path.join(ROOT, "tests"),
-                        "-I", os.path.join(ROOT, "uwimageproc_amd", "csrc"), os.path.join(ROOT, "tests", "png_decode_emulated.cpp"),
-                        "-o", self.exe, "-lz"], check=True, timeout=600)
+        self.d, self.count = d, 0
+        self.exe = eb.build(d, "png_decode.hip", "png_decode_emulated.cpp", "kernels_pngd.inc", eb.SANITIZE + ("-fno-sanitize-recover=all",),
+                            libs=("-lz",))
 
     def __call__(self, cases):
         """cases: [(name, stream, channels, segmented, chunk_bytes)] -> {(name, segmented, chunk_bytes): dict of the printed fields}"""
@@ -50,6 +44,21 @@ class Emu:
             v["tried"], v["valid"] = int(w[20 + n]), int(w[22 + n])
             out[(os.path.basename(w[0])[:-4], int(w[1]), int(w[2]))] = v
         assert len(out) == len(cases), stdout[-3000:]
+        return out
+
+    def batch(self, streams, ch, rows, cols, seg, cb):
+        """the streams in one call -> per frame the dict of the printed fields"""
+        paths = []
+        for i, stream in enumerate(streams):
+            paths.append(str(self.d / f"batch{i}.png"))
+            open(paths[-1], "wb").write(stream)
+        lst = str(self.d / "batch.txt")
+        open(lst, "w").write(f"batch {seg} {ch} {cb} {rows} {cols} " + " ".join(paths) + "\n")
+        r = subprocess.run([self.exe, lst], capture_output=True, text=True, timeout=1500)
+        assert r.returncode == 0, (r.stdout + r.stderr)[-3000:]
+        out = [{k: int(w[i]) for k, i in (("status", 6), ("single", 8), ("same", 10), ("clean", 12), ("accepted", 14), ("serial", 16))}
+               for w in map(str.split, r.stdout.splitlines())]
+        assert len(out) == len(streams), r.stdout[-3000:]
         return out
 
     def own(self, arr, filt=-1):

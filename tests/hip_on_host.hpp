@@ -1,16 +1,25 @@
-// HIP on host threads, for the emulation harnesses (jpeg_encode_emulated.cpp, jpeg_decode_emulated.cpp, png_decode_emulated.cpp):
-// enough of the device language for kernels cut out of a .hip file, and for a device header included as it stands
-// (csrc/png_inflate.hpp), to compile with the host compiler and run thread for thread -- one std::thread per GPU thread and a
-// barrier for __syncthreads, workgroups one after another.  Include it before the kernels.
+// HIP on host threads, for the emulation harnesses (*_emulated.cpp): enough of the device language for kernels cut out of a
+// .hip file, and for a device header included as it stands (csrc/png_inflate.hpp), to compile with the host compiler and run
+// thread for thread -- one std::thread per GPU thread and a barrier for __syncthreads, workgroups one after another -- and the
+// back end (HostThreads) on which a codec's own host sequence runs them.  Include it before the kernels.
 #pragma once
 #include <algorithm>
 #include <barrier>
 #include <cassert>
 #include <cstddef>
 #include <cstdint>
+#include <cstring>
+#include <functional>
+#include <map>
+#include <set>
+#include <string>
 #include <thread>
 #include <vector>
-struct d3 { unsigned x = 1, y = 1, z = 1; };
+struct dim3 {
+    unsigned x = 1, y = 1, z = 1;
+    dim3(unsigned x_ = 1, unsigned y_ = 1, unsigned z_ = 1) : x(x_), y(y_), z(z_) {}
+};
+using d3 = dim3;
 static thread_local d3 threadIdx, blockIdx, blockDim;
 static std::barrier<> *g_bar;
 #define __global__ static
@@ -48,18 +57,59 @@ static uint32_t block256_sum_u32(uint32_t v, uint32_t *)
     uint32_t s = 0; for (unsigned i = 0; i < 256; ++i) s += g_vals[i];
     __syncthreads(); return s;
 }
-// the grid, workgroup by workgroup; sync: the kernel uses __syncthreads (or atomics), so its threads run at the same time --
-// otherwise a plain loop over them
+// the grid, workgroup by workgroup; sync: the kernel uses __syncthreads (or atomics), so its threads run at the same time: one
+// host thread per GPU thread walks through all the workgroups, and a barrier between two of them keeps a fast thread out of
+// the next workgroup's shared memory -- otherwise a plain loop over the threads
 template <class F> static void launch(unsigned gx, unsigned gy, unsigned bs, bool sync, F f)
 {
-    for (unsigned by = 0; by < gy; ++by) for (unsigned bx = 0; bx < gx; ++bx) {
-        if (!sync) {
+    if (!sync) {
+        for (unsigned by = 0; by < gy; ++by) for (unsigned bx = 0; bx < gx; ++bx)
             for (unsigned t = 0; t < bs; ++t) { threadIdx.x = t; blockIdx.x = bx; blockIdx.y = by; blockDim.x = bs; f(); }
-            continue;
-        }
-        std::barrier<> bar(bs); g_bar = &bar;
-        std::vector<std::thread> th;
-        for (unsigned t = 0; t < bs; ++t) th.emplace_back([=, &bar] { g_bar = &bar; threadIdx.x = t; blockIdx.x = bx; blockIdx.y = by; blockDim.x = bs; f(); });
-        for (auto &t : th) t.join();
+        return;
     }
+    std::barrier<> bar(bs); g_bar = &bar;
+    std::vector<std::thread> th;
+    for (unsigned t = 0; t < bs; ++t)
+        th.emplace_back([=, &bar] {
+            threadIdx.x = t; blockDim.x = bs;
+            for (unsigned by = 0; by < gy; ++by) for (unsigned bx = 0; bx < gx; ++bx) {
+                blockIdx.x = bx; blockIdx.y = by;
+                f();
+                bar.arrive_and_wait();
+            }
+        });
+    for (auto &t : th) t.join();
 }
+
+// The back end of the codecs' host sequences (csrc/uwip_internal.hpp has the device's, uwip_device) on host threads: the
+// emulation harnesses hand it to the unit's own encode_sequence / decode_sequence, so the sanitizers check the array sizes,
+// the grid sizes and the order of the launches that ship.
+struct HostThreads {
+    using dim3 = ::dim3;
+    // every array is a heap block of its exact size, so that the address sanitizer sees an index one past any of them,
+    // filled with garbage: what a kernel reads it must have been given
+    std::map<std::string, std::vector<uint8_t>> arrays;
+    // kernels (by the name of the launch) that neither meet at a barrier nor use atomics: their threads run as a plain loop
+    std::set<std::string> barrier_free;
+    // the harness's look at a launch before it runs: taps on the arrays so far, a cap on the grid
+    std::function<void(const std::string &, dim3 &)> before_launch;
+    template <class T> T *array(const char *name, size_t count)
+    {
+        std::vector<uint8_t> &v = arrays[name];
+        v = std::vector<uint8_t>(count * sizeof(T), 0xDD);
+        return reinterpret_cast<T *>(v.data());
+    }
+    template <class T> const T *get(const char *name) const
+    {
+        const auto it = arrays.find(name);
+        return it == arrays.end() ? nullptr : reinterpret_cast<const T *>(it->second.data());
+    }
+    void fill(void *p, int value, size_t bytes) { if (bytes) std::memset(p, value, bytes); }
+    void copy(void *dst, const void *src, size_t bytes) { if (bytes) std::memcpy(dst, src, bytes); }
+    template <class... P, class... A> void launch(const char *name, void (*kernel)(P...), dim3 grid, unsigned block, A... args)
+    {
+        if (before_launch) before_launch(name, grid);
+        assert(grid.z == 1);
+        ::launch(grid.x, grid.y, block, !barrier_free.count(name), [=] { kernel(args...); });
+    }
+};

@@ -1,11 +1,14 @@
-// The kernels of uwimageproc_amd/csrc/jpeg_decode.hip executed on the host, thread for thread: one std::thread per GPU thread
-// and a barrier for __syncthreads in the kernels that synchronise, a plain loop over the threads in those that do not,
-// workgroups one after another, against jpeg::decode (cli/jpeg.hpp) into a strided, misaligned batch.  It checks the kernels'
-// logic (and, under the sanitizers, every index they form) where there is no device; the GPU tests check the compiled kernels.
-// tests/test_jpeg_decode_emulated.py cuts the kernels out of the .hip file into kernels_dec.inc (everything inside its
-// anonymous namespace), builds this file with the host compiler and gives it the streams:
+// uwimageproc_amd/csrc/jpeg_decode.hip executed on the host: the unit's own parse, plan and host sequence (decode_sequence) on
+// the host-thread back end of hip_on_host.hpp, so every kernel runs thread for thread -- one std::thread per GPU thread and a
+// barrier for __syncthreads in the kernels that synchronise, a plain loop over the threads in those that do not, workgroups
+// one after another -- against jpeg::decode (cli/jpeg.hpp) into a strided, misaligned batch.  It checks the kernels' logic and
+// the host sequence (under the sanitizers every index they form, every array size and grid) where there is no device; the GPU
+// tests check the compiled kernels.  tests/test_jpeg_decode_emulated.py cuts the unit's first anonymous namespace into
+// kernels_dec.inc, builds this file with the host compiler and gives it the streams:
 //   emu <list file>      one line per case: <path> <sync_rounds> <channels of the batch> [<file for the host decoder's pixels>]
+//                        or: batch <sync_rounds> <channels> <rows> <cols> <path>...     (all the streams in one call)
 // and prints per case: <path> <sync_rounds> status <s> host <0|1> equal <0|1> clean <0|1> unsettled <u> of <n>
+// per frame of a batch: batch <sync_rounds> frame <f> status <s> single <status alone> same <0|1> clean <0|1>
 #include <cstdio>
 #include <cstring>
 #include <fstream>
@@ -13,48 +16,60 @@
 #include "uwip.h"
 #include "jpeg.hpp"
 #include "jpeg_parse.hpp"
+#include "guarded_batch.hpp"
 #include "hip_on_host.hpp"
 #include "kernels_dec.inc"
-// uwip_jpeg_decode's host side for one frame, the kernels on host threads
-static int decode(const std::vector<uint8_t> &stream, int sync_rounds, uint8_t *out, size_t step, size_t fs, int rows, int cols, int channels,
-                  int32_t *status, unsigned long long *stats)
+// uwip_jpeg_decode on host threads: its parse and plan, then the unit's own decode_sequence.  stats: unsettled lanes, lanes
+static void decode(const std::vector<std::vector<uint8_t>> &streams, int sync_rounds, const uwip_batch_u8 &out, int32_t *status,
+                   unsigned long long *stats)
 {
-    const int n = 1, rounds = rounds_of(sync_rounds);
+    const int n = (int)streams.size();
     std::vector<DecFrame> fr(n);
-    size_t seg = 0;
-    std::memset(&fr[0], 0, sizeof(DecFrame));
-    int r = 0, c = 0, ch = 0;
-    fr[0].status = uwip_jpeg::parse(stream.data(), stream.size(), &r, &c, &ch, &fr[0], &seg);
-    if (fr[0].status == 0 && (r != rows || c != cols || (ch == 3 && channels == 1))) fr[0].status = UWIP_JPEG_SIZE_MISMATCH;
-    if (fr[0].status == 0) fr[0].seg_len = (uint32_t)(stream.size() - seg);
+    std::vector<size_t> seg(n, 0);
+    for (int f = 0; f < n; ++f) {
+        DecFrame &d = fr[f];
+        std::memset(&d, 0, sizeof d);
+        int r = 0, c = 0, ch = 0;
+        d.status = uwip_jpeg::parse(streams[f].data(), streams[f].size(), &r, &c, &ch, &d, &seg[f]);
+        if (d.status == 0 && (r != out.rows || c != out.cols || (ch == 3 && out.channels == 1))) d.status = UWIP_JPEG_SIZE_MISMATCH;
+        if (d.status == 0) d.seg_len = (uint32_t)(streams[f].size() - seg[f]);
+    }
     DecPlan pl;
     plan_layout(fr.data(), n, pl);
-    // exact sizes, so that the address sanitizer sees an index one past any of them
-    std::vector<uint8_t> src(pl.src_bytes, 0xEE), ubuf(pl.ubuf_bytes + 16, 0xEE), planes(pl.plane_bytes + 16, 0xEE);
-    if (fr[0].status == 0 && fr[0].seg_len) std::memcpy(src.data() + fr[0].seg_off, stream.data() + seg, fr[0].seg_len);
-    const size_t ni = pl.nintv + 1, ns = pl.nsub + 1;
-    std::vector<uint64_t> e0(ns, 0x5555), e1(ns, 0x5555), en(ns, 0x5555);
-    std::vector<uint32_t> cnt(ns, 77), sblk(ns, 77), sint(ns, 77), istart(ni, 77), isub(ni, 77), ifirst(ni, 0xFFFFFFFFu);
-    std::vector<int16_t> coef((pl.nblk + 1) * 64, 0);
-    int32_t err = 0;
-    stats[0] = stats[1] = 0;
-    DecBufs B;
-    B.fr = fr.data(); B.src = src.data(); B.ubuf = ubuf.data();
-    B.exit0 = e0.data(); B.exit1 = e1.data(); B.entry = en.data(); B.stats = stats;
-    B.cnt = cnt.data(); B.sblk = sblk.data(); B.sint = sint.data(); B.istart = istart.data(); B.isub = isub.data(); B.ifirst = ifirst.data();
-    B.coef = coef.data(); B.planes = planes.data(); B.status = status; B.err = &err;
-    const unsigned gsub = uwip_cdiv(pl.max_sub ? pl.max_sub : 1, 256), gint = uwip_cdiv(pl.max_int ? pl.max_int : 1, 64);
-    const unsigned gblk = uwip_cdiv(pl.max_blk ? pl.max_blk : 1, 64), gpix = uwip_cdiv((size_t)rows * cols, 256);
-    launch(n, 1, 256, true, [=] { k_jpd_unstuff(B); });
-    for (int rr = 0; rr <= rounds; ++rr) launch(gsub, n, 256, true, [=] { k_jpd_round(B, rr); });
-    launch(gsub, n, 256, true, [=] { k_jpd_check(B, rounds); });
-    launch(gint, n, 64, true, [=] { k_jpd_cleanup(B, rounds); });
-    launch(n, 1, 256, true, [=] { k_jpd_blkscan(B); });
-    launch(gsub, n, 256, true, [=] { k_jpd_write(B, rounds); });
-    launch(3, n, 256, true, [=] { k_jpd_dc(B); });
-    launch(gblk, n, 64, false, [=] { k_jpd_idct(B); });
-    launch(gpix, n, 256, false, [=] { k_jpd_color(B, out, step, fs, rows, cols, channels); });
-    return 0;
+    std::vector<uint8_t> src(pl.src_bytes, 0xEE);              // its exact size, as the back end's arrays have theirs
+    for (int f = 0; f < n; ++f)
+        if (fr[f].status == 0 && fr[f].seg_len) std::memcpy(src.data() + fr[f].seg_off, streams[f].data() + seg[f], fr[f].seg_len);
+    HostThreads be;
+    be.barrier_free = {"k_jpd_idct", "k_jpd_color"};
+    decode_sequence(be, fr.data(), src.data(), pl, n, rounds_of(sync_rounds), out, status, stats);
+}
+
+static std::vector<uint8_t> read_file(const std::string &path)
+{
+    std::ifstream f(path, std::ios::binary);
+    return std::vector<uint8_t>((std::istreambuf_iterator<char>(f)), std::istreambuf_iterator<char>());
+}
+
+// batch <sync_rounds> <channels> <rows> <cols> <path>...: the streams in one call, and each alone into a batch of the same shape
+static void batch_case(std::istringstream &is)
+{
+    int rounds = -1, channels = 3, rows = 0, cols = 0;
+    is >> rounds >> channels >> rows >> cols;
+    std::vector<std::vector<uint8_t>> streams;
+    for (std::string path; is >> path;) streams.push_back(read_file(path));
+    const int n = (int)streams.size();
+    Batch all(n, rows, cols, channels);
+    std::vector<int32_t> status(n, 99);
+    unsigned long long stats[2];
+    decode(streams, rounds, all.b, status.data(), stats);
+    for (int f = 0; f < n; ++f) {
+        Batch one(1, rows, cols, channels);
+        int32_t st1 = 99;
+        decode({streams[f]}, rounds, one.b, &st1, stats);
+        bool same = true;
+        for (int y = 0; y < rows; ++y) same = same && !std::memcmp(all.row(f, y), one.row(0, y), (size_t)cols * channels);
+        std::printf("batch %d frame %d status %d single %d same %d clean %d\n", rounds, f, status[f], st1, (int)same, (int)(all.clean() && one.clean()));
+    }
 }
 int main(int argc, char **argv)
 {
@@ -64,10 +79,11 @@ int main(int argc, char **argv)
     while (std::getline(list, line)) {
         std::istringstream is(line);
         std::string path, dump; int rounds = -1, channels = 3;
-        if (!(is >> path >> rounds >> channels)) continue;
+        if (!(is >> path)) continue;
+        if (path == "batch") { batch_case(is); continue; }
+        if (!(is >> rounds >> channels)) continue;
         is >> dump;
-        std::ifstream f(path, std::ios::binary);
-        std::vector<uint8_t> s((std::istreambuf_iterator<char>(f)), std::istreambuf_iterator<char>());
+        const std::vector<uint8_t> s = read_file(path);
         int rows = 0, cols = 0, ch = 0;
         std::vector<uint8_t> host;
         const bool host_ok = jpeg::decode(s.data(), s.size(), rows, cols, ch, host, channels == 3);
@@ -75,19 +91,13 @@ int main(int argc, char **argv)
         int32_t ir = 0, ic = 0, ich = 0;
         const int info = uwip_jpeg::parse(s.data(), s.size(), &ir, &ic, &ich, nullptr, nullptr);
         if (!host_ok) { rows = info == 0 ? ir : 8; cols = info == 0 ? ic : 8; }
-        const size_t step = (size_t)cols * channels + 5, fs = step * rows + 77;
-        std::vector<uint8_t> buf(fs + 3, 0xA5);
-        uint8_t *out = buf.data() + 3;
+        Batch bt(1, rows, cols, channels);
         int32_t status = 99;
         unsigned long long stats[2];
-        decode(s, rounds, out, step, fs, rows, cols, channels, &status, stats);
-        bool equal = host_ok && status == 0, clean = true;
-        for (int y = 0; y < rows && equal; ++y) equal = !std::memcmp(out + y * step, host.data() + (size_t)y * cols * channels, (size_t)cols * channels);
-        for (size_t i = 0; i < buf.size(); ++i) {
-            const size_t o = i < 3 ? SIZE_MAX : i - 3;
-            const bool inside = o != SIZE_MAX && o / step < (size_t)rows && o % step < (size_t)cols * channels;
-            if (!inside && buf[i] != 0xA5) clean = false;
-        }
+        decode({s}, rounds, bt.b, &status, stats);
+        bool equal = host_ok && status == 0;
+        for (int y = 0; y < rows && equal; ++y) equal = !std::memcmp(bt.row(0, y), host.data() + (size_t)y * cols * channels, (size_t)cols * channels);
+        const bool clean = bt.clean();
         std::printf("%s %d status %d host %d equal %d clean %d unsettled %llu of %llu\n", path.c_str(), rounds, status, (int)host_ok, (int)equal, (int)clean, stats[0], stats[1]);
     }
     return 0;

@@ -1,9 +1,10 @@
-// The kernels of uwimageproc_amd/csrc/jpeg_encode.hip executed on the host, thread for thread: one std::thread per GPU thread, a
-// barrier for __syncthreads, workgroups one after another, against jpeg::encode (cli/jpeg.hpp) on strided, misaligned batches,
-// with slots that fit, are one byte short, or are far too small.  It checks the kernels' logic where there is no device; the
-// GPU tests check the compiled kernels.  tests/test_jpeg_encode_emulated.py cuts the kernels out of the .hip file into
-// kernels.inc (everything inside its anonymous namespace) and builds this file with the host compiler; hip_on_host.hpp is the
-// device language on host threads.
+// uwimageproc_amd/csrc/jpeg_encode.hip executed on the host: the unit's own host sequence (encode_sequence) on the host-thread
+// back end of hip_on_host.hpp, so every kernel runs thread for thread -- one std::thread per GPU thread, a barrier for
+// __syncthreads, workgroups one after another -- against jpeg::encode (cli/jpeg.hpp) on strided, misaligned batches, with slots
+// that fit, are one byte short, or are far too small, and once with a frame count below the batch.  It checks the kernels' logic
+// and the host sequence where there is no device; the GPU tests check the compiled kernels.
+// tests/test_jpeg_encode_emulated.py cuts the unit's first anonymous namespace into kernels.inc and builds this file with the
+// host compiler.
 #include <cmath>
 #include <cstdio>
 #include <cstring>
@@ -13,45 +14,17 @@
 #include "jpeg_tables.hpp"
 #include "hip_on_host.hpp"
 #include "kernels.inc"
-static int encode(const uint8_t *img, int F, int rows, int cols, int nc, size_t step, size_t fs, int quality, uint8_t *d_streams, size_t slot_bytes, int64_t *d_sizes)
+// uwip_jpeg_encode_dev on host threads: its tables as host structs, then the unit's own encode_sequence.  count: null, or the
+// frame count that the kernels read
+static void encode(const uint8_t *img, int F, int rows, int cols, int nc, size_t step, size_t fs, int quality, uint8_t *d_streams, size_t slot_bytes,
+                   int64_t *d_sizes, const int32_t *count = nullptr)
 {
-    quality = clamp_quality(quality);
     Geo g; g.rows = rows; g.cols = cols; g.nc = nc; g.step = step; g.fs = fs; g.nblk = blocks_of(rows, cols, nc, &g.mcux);
-    static JpegHuff H; std::memset(&H, 0, sizeof H);
-    { using namespace uwip_jpeg; uint32_t t[256];
-      build_codes(DC_LUM_BITS, DC_VALS, t); std::memcpy(H.dc[0], t, sizeof H.dc[0]);
-      build_codes(DC_CHR_BITS, DC_VALS, t); std::memcpy(H.dc[1], t, sizeof H.dc[1]);
-      build_codes(AC_LUM_BITS, AC_LUM_VALS, H.ac[0]); build_codes(AC_CHR_BITS, AC_CHR_VALS, H.ac[1]); }
-    static JpegConst Cn; std::memset(&Cn, 0, sizeof Cn); build_const(rows, cols, nc, quality, Cn);
-    const JpegHuff *huff = &H; const JpegConst *cst = &Cn;
-    const int nwg_bits = (int)uwip_cdiv((size_t)g.nblk, kBitsWG), nwg_emit = (int)uwip_cdiv((size_t)g.nblk, kEmitWG);
-    const size_t ubound = ((size_t)g.nblk * kMaxBlockBits + 7) / 8;
-    const size_t ucap = slot_bytes < ubound ? slot_bytes : ubound;
-    const size_t ustride = ((ucap + 15) / 16) * 4 + 8;
-    const int nchunk = ucap ? (int)uwip_cdiv(ucap, kChunk) : 1;
-    std::vector<int16_t> coefv((size_t)F * g.nblk * 64 + 8);
-    int16_t *coef = (int16_t *)(((uintptr_t)coefv.data() + 15) & ~(uintptr_t)15);
-    std::vector<uint32_t> ubufv((size_t)F * ustride + 4, 0xDEADBEEFu);      // garbage: only the shared words get zeroed
-    uint32_t *ubuf = (uint32_t *)(((uintptr_t)ubufv.data() + 15) & ~(uintptr_t)15);
-    std::vector<uint32_t> blkoffv((size_t)F * g.nblk); uint32_t *blkoff = blkoffv.data();
-    const size_t n64 = (size_t)F * nwg_bits + F + (size_t)F * nchunk + F;
-    const size_t n32 = (size_t)F * nwg_bits + (size_t)F * nchunk + F + (size_t)F * (nwg_emit + 1);
-    std::vector<uint64_t> metav(n64 + n32 / 2 + 2, 0x5555555555555555ull); uint64_t *meta = metav.data();
-    uint64_t *wgbase = meta, *totbits = wgbase + (size_t)F * nwg_bits, *chunkbase = totbits + F;
-    int64_t *needed = reinterpret_cast<int64_t *>(chunkbase + (size_t)F * nchunk);
-    uint32_t *wgsum = reinterpret_cast<uint32_t *>(needed + F), *chunkcnt = wgsum + (size_t)F * nwg_bits;
-    uint32_t *ffemit = chunkcnt + (size_t)F * nchunk, *notff = ffemit + F;
-    std::memset(ffemit, 0, ((size_t)F + (size_t)F * (nwg_emit + 1)) * sizeof(uint32_t));
-    const Offs o{blkoff, wgbase, totbits, nwg_bits};
-    launch(nwg_bits, F, 256, true, [=] { k_jpeg_transform(img, g, cst, coef); });
-    launch(nwg_bits, F, kBitsWG, true, [=] { k_jpeg_bits(coef, g, huff, blkoff, wgsum, nwg_bits); });
-    launch(F, 1, 256, true, [=] { k_jpeg_scan_bits(wgsum, wgbase, totbits, nwg_bits); });
-    launch(uwip_cdiv((size_t)nwg_emit, 256), F, 256, true, [=] { k_jpeg_zero_shared(g, o, cst, slot_bytes, ubuf, ustride, nwg_emit); });
-    launch(nwg_emit, F, kEmitWG, true, [=] { k_jpeg_emit(coef, g, huff, o, cst, slot_bytes, ubuf, ustride, ffemit, notff, nwg_emit); });
-    launch(nchunk, F, 256, true, [=] { k_jpeg_ffcount(ubuf, ustride, totbits, cst, slot_bytes, chunkcnt, nchunk); });
-    launch(F, 1, 256, true, [=] { k_jpeg_finish(chunkcnt, chunkbase, nchunk, g, o, cst, ffemit, notff, nwg_emit, needed); });
-    launch(nchunk, F, 256, true, [=] { k_jpeg_assemble(ubuf, ustride, totbits, chunkbase, nchunk, cst, needed, d_streams, slot_bytes, d_sizes); });
-    return 0;
+    static JpegHuff H; build_huff(H);
+    static JpegConst Cn; std::memset(&Cn, 0, sizeof Cn); build_const(rows, cols, nc, clamp_quality(quality), Cn);
+    HostThreads be;
+    be.barrier_free = {"k_jpeg_zero_shared"};
+    encode_sequence(be, img, g, F, &H, &Cn, d_streams, slot_bytes, d_sizes, count);
 }
 int main()
 {
@@ -92,6 +65,19 @@ int main()
                 if (!ok) { ++bad; std::printf("MISMATCH %dx%dx%d q%d kind %d mode %d frame %d: size %lld want %lld\n", c.rows, c.cols, c.nc, c.q, c.kind, mode, f, (long long)sizes[f], (long long)want); }
             }
             for (size_t i = slot * F; i < out.size(); ++i) if (out[i] != 0xEE) { ++bad; std::printf("wrote past the end\n"); break; }
+        }
+        if (c.rows == 7 && c.nc == 3 && c.q == 50 && c.kind == 2) {
+            // a device count below the batch: frame 0 as ever, frame 1 reports size 0, its slot and all behind it stay untouched
+            const size_t slot = std::max(host[0].size(), host[1].size()) + 9;
+            std::vector<uint8_t> out(slot * F + 8, 0xEE);
+            int64_t sizes[2] = {-77, -77};
+            const int32_t count = 1;
+            encode(img, F, c.rows, c.cols, c.nc, step, fs, c.q, out.data(), slot, sizes, &count);
+            ++ncase;
+            bool ok = sizes[0] == (int64_t)host[0].size() && sizes[1] == 0 && !std::memcmp(out.data(), host[0].data(), host[0].size());
+            for (size_t i = slot; i < out.size(); ++i) ok = ok && out[i] == 0xEE;
+            if (!ok) { ++bad; std::printf("MISMATCH count 1 of 2: sizes %lld %lld want %zu 0\n", (long long)sizes[0], (long long)sizes[1], host[0].size()); }
+            else std::printf("count 1 of 2 ok\n");
         }
     }
     std::printf("%d cases, %d mismatches\n", ncase, bad);

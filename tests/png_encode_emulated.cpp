@@ -1,9 +1,10 @@
-// The kernels of uwimageproc_amd/csrc/png_encode.hip executed on the host, thread for thread: one std::thread per GPU thread, a
-// barrier for __syncthreads, workgroups one after another, against the serial reference encoder (csrc/png_reference.hpp) on
-// strided, misaligned batches, every filter choice, with slots that fit, are one byte short, or are far too small.  It checks
-// the kernels' parallel structure where there is no device; the GPU tests check the compiled kernels.
-// tests/test_png_encode_emulated.py cuts the kernels out of the .hip file into kernels.inc (everything inside its anonymous
-// namespace), builds this file with the host compiler and the address and undefined-behaviour sanitizers, and then checks the
+// uwimageproc_amd/csrc/png_encode.hip executed on the host: the unit's own host sequence (encode_sequence) on the host-thread
+// back end of hip_on_host.hpp, so every kernel runs thread for thread -- one std::thread per GPU thread, a barrier for
+// __syncthreads, workgroups one after another -- against the serial reference encoder (csrc/png_reference.hpp) on strided,
+// misaligned batches, every filter choice, with slots that fit, are one byte short, or are far too small, and once with a frame
+// count below the batch.  It checks the kernels' parallel structure and the host sequence where there is no device; the GPU
+// tests check the compiled kernels.  tests/test_png_encode_emulated.py cuts the unit's first anonymous namespace into
+// kernels.inc, builds this file with the host compiler and the address and undefined-behaviour sanitizers, and then checks the
 // streams this program leaves in the directory argv[1] with Pillow, zlib and numpy: <case>.png, <case>.raw (the packed input)
 // and manifest.txt (case rows cols channels filter).
 #include <cmath>
@@ -16,71 +17,16 @@
 #include "png_reference.hpp"
 #include "kernels.inc"
 
-// hip_on_host.hpp's launch starts 256 threads per workgroup; here the 256 threads of a launch walk through all its workgroups
-// (a barrier between two of them keeps a fast thread out of the next workgroup's shared memory)
-template <class Fn> static void launch_grid(unsigned gx, unsigned gy, Fn f)
+// uwip_png_encode_dev on host threads: the head bytes in host memory, then the unit's own encode_sequence.  count: null, or the
+// frame count that the kernels read
+static void encode(const uint8_t *img, int F, int rows, int cols, int nc, size_t step, size_t fs, int filter, uint8_t *streams, size_t slot_bytes,
+                   int64_t *sizes, const int32_t *count = nullptr)
 {
-    std::barrier<> bar(256);
-    std::vector<std::thread> th;
-    for (unsigned t = 0; t < 256; ++t)
-        th.emplace_back([=, &bar] {
-            g_bar = &bar; threadIdx.x = t; blockDim.x = 256;
-            for (unsigned by = 0; by < gy; ++by) for (unsigned bx = 0; bx < gx; ++bx) {
-                blockIdx.x = bx; blockIdx.y = by;
-                f();
-                bar.arrive_and_wait();
-            }
-        });
-    for (auto &t : th) t.join();
-}
-
-struct Prepared {
-    PGeo g;
-    int F;
-    std::vector<uint8_t> filt, stage;
-    std::vector<uint64_t> coff;
-    std::vector<int64_t> needed;
-    std::vector<ChunkOut> cout;
-    std::vector<uint32_t> adler;
+    const PGeo g = geometry_of(rows, cols, nc, step, fs);
     uint8_t head[kHeadBytes];
-};
-
-// everything of uwip_png_encode that does not depend on the slot
-static void prepare(const uint8_t *img, int F, int rows, int cols, int nc, size_t step, size_t fs, int filter, Prepared &P)
-{
-    PGeo &g = P.g;
-    g.rows = rows; g.cols = cols; g.nc = nc; g.step = step; g.fs = fs;
-    g.total = filtered_bytes(rows, cols, nc);
-    g.nch = (int)chunks_of(g.total);
-    g.fstride = (size_t)g.nch * kChunk;
-    P.F = F;
-    const size_t nchunks = (size_t)F * g.nch;
-    P.filt.assign((size_t)F * g.fstride, 0xCD);             // garbage: bytes past a frame's end are never read as data
-    P.stage.assign(nchunks * kStageBytes, 0xAB);
-    P.coff.assign(nchunks, 0x5555555555555555ull);
-    P.needed.assign(F, -1);
-    P.cout.assign(nchunks, ChunkOut{7, 7, 7, 7});
-    P.adler.assign(F, 7);
-    write_head(rows, cols, nc, P.head);
-    uint8_t *filt = P.filt.data(), *stage = P.stage.data();
-    ChunkOut *cout = P.cout.data();
-    uint64_t *coff = P.coff.data();
-    int64_t *needed = P.needed.data();
-    uint32_t *adler = P.adler.data();
-    const PGeo gg = g;
-    launch_grid(rows, F, [=] { k_png_filter(img, gg, filter, filt); });
-    launch_grid(gg.nch, F, [=] { k_png_deflate(filt, gg, stage, cout); });
-    launch_grid(F, 1, [=] { k_png_finish(cout, gg, coff, needed, adler); });
-}
-static void assemble(const Prepared &P, uint8_t *streams, size_t slot_bytes, int64_t *sizes)
-{
-    const uint8_t *stage = P.stage.data(), *head = P.head;
-    const ChunkOut *cout = P.cout.data();
-    const uint64_t *coff = P.coff.data();
-    const int64_t *needed = P.needed.data();
-    const uint32_t *adler = P.adler.data();
-    const PGeo gg = P.g;
-    launch_grid(gg.nch, P.F, [=] { k_png_assemble(stage, cout, coff, gg, head, needed, adler, streams, slot_bytes, sizes); });
+    write_head(rows, cols, nc, head);
+    HostThreads be;
+    encode_sequence(be, img, g, F, filter, head, streams, slot_bytes, sizes, count);
 }
 
 static bool dump(const std::string &path, const uint8_t *p, size_t n)
@@ -146,14 +92,12 @@ int main(int argc, char **argv)
                 uwip_png::encode_host_reference(packed[f].data(), c.rows, c.cols, c.nc, rb, filter, ref[f]);
                 longest = std::max(longest, ref[f].size());
             }
-            static Prepared P;
-            prepare(img, F, c.rows, c.cols, c.nc, step, fs, filter, P);
             for (int mode = 0; mode < 3; ++mode) {
                 // 0: generous slot; 1: frame 0 one byte short; 2: frame 0 far too small
                 const size_t slot = mode == 0 ? longest + 9 : mode == 1 ? ref[0].size() - 1 : ref[0].size() / 2;
                 std::vector<uint8_t> out(slot * F + 8, 0xEE);
                 std::vector<int64_t> sizes(F, 0);
-                assemble(P, out.data(), slot, sizes.data());
+                encode(img, F, c.rows, c.cols, c.nc, step, fs, filter, out.data(), slot, sizes.data());
                 ++ncase;
                 for (int f = 0; f < F; ++f) {
                     const bool fit = ref[f].size() <= slot;
@@ -179,6 +123,19 @@ int main(int argc, char **argv)
                     }
                 }
                 for (size_t i = slot * F; i < out.size(); ++i) if (out[i] != 0xEE) { ++bad; std::printf("wrote past the end\n"); break; }
+            }
+            if (c.rows == 5 && c.nc == 3 && filter == -1) {
+                // two frames and a device count of 1: frame 0 as ever, frame 1 reports size 0, its slot and all behind it stay untouched
+                const size_t slot = longest + 9;
+                std::vector<uint8_t> out(slot * 2 + 8, 0xEE);
+                int64_t sizes[2] = {-77, -77};
+                const int32_t count = 1;
+                encode(img, 2, c.rows, c.cols, c.nc, step, fs, filter, out.data(), slot, sizes, &count);
+                ++ncase;
+                bool ok = sizes[0] == (int64_t)ref[0].size() && sizes[1] == 0 && !std::memcmp(out.data(), ref[0].data(), ref[0].size());
+                for (size_t i = ref[0].size(); i < out.size(); ++i) ok = ok && out[i] == 0xEE;
+                if (!ok) { ++bad; std::printf("MISMATCH count 1 of 2: sizes %lld %lld want %zu 0\n", (long long)sizes[0], (long long)sizes[1], ref[0].size()); }
+                else std::printf("count 1 of 2 ok\n");
             }
         }
     }

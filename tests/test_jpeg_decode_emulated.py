@@ -7,24 +7,15 @@ import subprocess
 import numpy as np
 import pytest
 
+import _emu_build as eb
 import _jpeg_forge_cases as fc
 import _jpeg_streams as js
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 @pytest.fixture(scope="module")
 def emu(tmp_path_factory):
     d = tmp_path_factory.mktemp("jpd_emu")
-    src = open(os.path.join(ROOT, "uwimageproc_amd", "csrc", "jpeg_decode.hip")).read()
-    a, end = src.index("namespace {"), "}  // namespace\n"
-    b = src.index(end)
-    open(str(d / "kernels_dec.inc"), "w").write(src[a:b + len(end)])
-    exe = str(d / "emu")
-    subprocess.run(["g++", "-std=c++20", "-O1", "-pthread", "-w", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                    "-I", str(d), "-I", os.path.join(ROOT, "include"), "-I", os.path.join(ROOT, "cli"),
-                    "-I", os.path.join(ROOT, "uwimageproc_amd", "csrc"), os.path.join(ROOT, "tests", "jpeg_decode_emulated.cpp"),
-                    "-o", exe], check=True, timeout=600)
+    exe = eb.build(d, "jpeg_decode.hip", "jpeg_decode_emulated.cpp", "kernels_dec.inc", eb.SANITIZE + ("-fno-sanitize-recover=all",))
 
     def run(cases, dump=False):
         """cases: [(name, stream, channels, rounds)] -> {(name, rounds): dict of the printed fields}; with `dump` also
@@ -50,6 +41,21 @@ def emu(tmp_path_factory):
             p = str(d / (name + ".host"))
             v["pixels"] = open(p, "rb").read() if os.path.exists(p) else None
         return out
+
+    def batch(streams, ch, rows, cols, rounds):
+        """the streams in one call -> per frame the dict of the printed fields"""
+        paths = []
+        for i, stream in enumerate(streams):
+            paths.append(str(d / f"batch{i}.jpg"))
+            open(paths[-1], "wb").write(stream)
+        lst = str(d / "batch.txt")
+        open(lst, "w").write(f"batch {rounds} {ch} {rows} {cols} " + " ".join(paths) + "\n")
+        r = subprocess.run([exe, lst], capture_output=True, text=True, timeout=1500)
+        assert r.returncode == 0, (r.stdout + r.stderr)[-3000:]
+        out = [{"status": int(w[5]), "single": int(w[7]), "same": int(w[9]), "clean": int(w[11])} for w in map(str.split, r.stdout.splitlines())]
+        assert len(out) == len(streams), r.stdout[-3000:]
+        return out
+    run.batch = batch
     return run
 
 
@@ -71,6 +77,21 @@ def test_every_kind_at_every_round_count(emu):
     # the noise frame spans many subsequences, and the sync rounds settle them
     assert res[("noise_s0", -1)]["lanes"] > 100
     assert res[("noise_s0", 0)]["unsettled"] > res[("noise_s0", -1)]["unsettled"]
+
+
+def test_a_batch_in_one_call_equals_its_streams_alone(emu):
+    """Four streams into one 17 x 33 batch: every per-frame base of the plan is non-zero somewhere, and the 16 x 16 stream, which
+    the host refuses (SIZE_MISMATCH), takes no room.  Each frame must have the status and the bytes that the same stream gets
+    alone -- the form every other test here holds to the host decoder -- and nothing else is written."""
+    img = js.content(17, 33)
+    s444 = js.pil_stream(img, 95, 0)
+    a = js.segment_start(s444)
+    streams = [js.pil_stream(img, 95, 2), js.pil_stream(js.content(16, 16), 95, 2), js.pil_stream(np.ascontiguousarray(img[..., 1]), 95),
+               s444[:a + (len(s444) - a) // 2]]
+    for rounds in (0, -1):
+        res = emu.batch(streams, 3, 17, 33, rounds)
+        assert [v["status"] for v in res] == [0, -2, 0, 0], res
+        assert all(v["status"] == v["single"] and v["same"] and v["clean"] for v in res), res
 
 
 def test_truncated_streams_follow_the_host_decoder(emu):

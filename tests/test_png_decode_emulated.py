@@ -18,7 +18,7 @@ def emu(tmp_path_factory):
     def run(cases):
         """cases: [(name, stream, channels, segmented)] -> {(name, segmented): dict of the printed fields}"""
         return {(name, seg): v for (name, seg, _), v in e([c + (0,) for c in cases]).items()}
-    run.own = e.own
+    run.own, run.batch = e.own, e.batch
     return run
 
 
@@ -83,6 +83,21 @@ def test_two_and_three_segments_on_both_paths(emu):
     assert res[("p97_sync", 1)]["serial"] == 1 and res[("p97_sync", 1)]["accepted"] < 3          # refused: it reaches back
     assert res[("m_full10k_mix", 1)]["serial"] == 1 and res[("m_full10k_mix", 1)]["accepted"] < 4   # refused: 10000-byte windows
     assert res[("g_full10k", 1)]["serial"] == 1
+
+
+def test_a_batch_in_one_call_equals_its_streams_alone(emu):
+    """Four streams into one 17 x 33 batch, with the segments (1) and the found block starts at 256-byte chunks (2): every
+    per-frame base of the plan is non-zero somewhere, and the 16 x 16 stream, which the host refuses (SIZE_MISMATCH), takes no
+    room.  Each frame must have the status and the bytes that the same stream gets alone -- the form every other test here
+    holds to the host reader -- and nothing else is written."""
+    own = emu.own(pd.content(17, 33, 3, "noise")[..., ::-1].copy())
+    a, b = pd.idat_span(own)
+    assert b - a >= 1700                                        # stored: at least two chunks of 256 bytes
+    streams = [own, pd.pil_stream(pd.content(16, 16, 3)), pd.pil_stream(pd.content(17, 33, 2)), own[:len(own) // 2]]
+    for seg, cb in ((1, 0), (2, 256)):
+        res = emu.batch(streams, 3, 17, 33, seg, cb)
+        assert [v["status"] for v in res] == [0, -2, 0, -1], res
+        assert all(v["status"] == v["single"] and v["same"] and v["clean"] for v in res), res
 
 
 def _follows_host(res):

@@ -2,29 +2,21 @@
 undefined-behaviour sanitizers) and must write the serial reference encoder's bytes -- sizes, streams, the negative size of a
 frame that does not fit, nothing past a slot.  Every stream it leaves is then checked without this project's code: Pillow's
 pixels, zlib's inflate against the numpy restatement of the filter rule, and the bound."""
-import os
 import subprocess
 
 import numpy as np
 
+import _emu_build as eb
 import _png_streams as ps
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def test_kernels_on_host_threads_equal_the_reference_and_decode(tmp_path):
-    src = open(os.path.join(ROOT, "uwimageproc_amd", "csrc", "png_encode.hip")).read()
-    a, end = src.index("namespace {"), "}  // namespace\n"
-    b = src.index(end)
-    open(str(tmp_path / "kernels.inc"), "w").write(src[a:b + len(end)])
-    exe = str(tmp_path / "emu")
-    subprocess.run(["g++", "-std=c++20", "-O1", "-g", "-pthread", "-w", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
-                    "-I", str(tmp_path), "-I", os.path.join(ROOT, "tests"), "-I", os.path.join(ROOT, "uwimageproc_amd", "csrc"),
-                    os.path.join(ROOT, "tests", "png_encode_emulated.cpp"), "-o", exe], check=True, timeout=600)
+    exe = eb.build(tmp_path, "png_encode.hip", "png_encode_emulated.cpp", flags=eb.SANITIZE + ("-g", "-fno-sanitize-recover=undefined"), include=())
     out = tmp_path / "streams"
     out.mkdir()
     r = subprocess.run([exe, str(out)], capture_output=True, text=True, timeout=1200)
     assert r.returncode == 0 and " 0 mismatches" in r.stdout, r.stdout[-3000:] + r.stderr[-3000:]
+    assert "count 1 of 2 ok" in r.stdout          # the case with a device count below the batch ran
 
     import uwimageproc_amd as uw
     lines = open(str(out / "manifest.txt")).read().split("\n")[:-1]

@@ -1,30 +1,21 @@
 """CPU: the kernels of csrc/strip.hip run on host threads (tests/strip_emulated.cpp, a stand-alone program built with
 -fsanitize=address,undefined -ffp-contract=off) and must give the numpy mirror's chain outputs, canvases and cover planes,
 exactly, on cases A-C of tests/_strip_cases.py."""
-import os
 import subprocess
 
 import numpy as np
 import pytest
 
+import _emu_build as eb
 import _strip_cases as cases
 import _strip_mirror as sm
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 @pytest.fixture(scope="module")
 def emu(tmp_path_factory):
     d = tmp_path_factory.mktemp("strip_emu")
-    src = open(os.path.join(ROOT, "uwimageproc_amd", "csrc", "strip.hip")).read()
-    a, end = src.index("namespace {"), "}  // namespace\n"
-    b = src.index(end)
-    open(str(d / "kernels.inc"), "w").write(src[a:b + len(end)])
-    exe = str(d / "emu")
-    subprocess.run(["g++", "-std=c++20", "-O1", "-g", "-pthread", "-w", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
-                    "-ffp-contract=off", "-I", str(d), "-I", os.path.join(ROOT, "include"), "-I", os.path.join(ROOT, "tests"),
-                    "-I", os.path.join(ROOT, "uwimageproc_amd", "csrc"), os.path.join(ROOT, "tests", "strip_emulated.cpp"), "-o", exe],
-                   check=True, timeout=600)
+    exe = eb.build(d, "strip.hip", "strip_emulated.cpp", flags=eb.SANITIZE + ("-g", "-fno-sanitize-recover=undefined", "-ffp-contract=off"),
+                   include=("include",))
     return exe, d
 
 

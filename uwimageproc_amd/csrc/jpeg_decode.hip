@@ -577,6 +577,50 @@ void plan_layout(DecFrame *fr, int F, DecPlan &pl)
 
 int rounds_of(int sync_rounds) { return sync_rounds < 0 ? kDefaultRounds : (sync_rounds > 64 ? 64 : sync_rounds); }
 
+// uwip_jpeg_decode behind the upload, on either back end (uwip_device; the host threads of tests/hip_on_host.hpp): the working
+// arrays, their first values and every launch.  fr / src: the planned descriptors and the segments, where the kernels read them.
+template <class BE>
+void decode_sequence(BE &be, const DecFrame *fr, const uint8_t *src, const DecPlan &pl, int n, int rounds, const uwip_batch_u8 &out,
+                     int32_t *d_status, void *d_unsettled)
+{
+    using dim3 = typename BE::dim3;                           // HIP's on the device, its stand-in on host threads
+    const size_t ni = pl.nintv + 1, ns = pl.nsub + 1, ncoef = (pl.nblk + 1) * 64;
+    DecBufs B;
+    B.fr = fr; B.src = src; B.status = d_status;
+    B.ubuf = be.template array<uint8_t>("jpegdec.unstuffed", pl.ubuf_bytes + 16);
+    B.istart = be.template array<uint32_t>("jpegdec.istart", ni);
+    B.isub = be.template array<uint32_t>("jpegdec.isub", ni);
+    B.ifirst = be.template array<uint32_t>("jpegdec.ifirst", ni);
+    B.exit0 = be.template array<uint64_t>("jpegdec.exit0", ns);
+    B.exit1 = be.template array<uint64_t>("jpegdec.exit1", ns);
+    B.entry = be.template array<uint64_t>("jpegdec.entry", ns);
+    B.cnt = be.template array<uint32_t>("jpegdec.cnt", ns);
+    B.sblk = be.template array<uint32_t>("jpegdec.sblk", ns);
+    B.sint = be.template array<uint32_t>("jpegdec.sint", ns);
+    B.coef = be.template array<int16_t>("jpegdec.coef", ncoef);
+    B.planes = be.template array<uint8_t>("jpegdec.planes", pl.plane_bytes + 16);
+    B.err = be.template array<int32_t>("jpegdec.err", (size_t)n);
+    B.stats = be.template array<unsigned long long>("jpegdec.stats", 2);
+    be.fill(B.err, 0, (size_t)n * sizeof(int32_t));
+    be.fill(B.stats, 0, 2 * sizeof(unsigned long long));
+    be.fill(B.ifirst, 0xFF, ni * sizeof(uint32_t));
+    be.fill(B.coef, 0, ncoef * sizeof(int16_t));
+
+    const unsigned gsub = uwip_cdiv(pl.max_sub ? pl.max_sub : 1, 256), gint = uwip_cdiv(pl.max_int ? pl.max_int : 1, 64);
+    const unsigned gblk = uwip_cdiv(pl.max_blk ? pl.max_blk : 1, 64), gpix = uwip_cdiv((size_t)out.rows * out.cols, 256);
+    be.launch("k_jpd_unstuff", k_jpd_unstuff, dim3(n), 256, B);
+    for (int r = 0; r <= rounds; ++r) be.launch(r ? "k_jpd_round_sync" : "k_jpd_round", k_jpd_round, dim3(gsub, n), 256, B, r);
+    be.launch("k_jpd_check", k_jpd_check, dim3(gsub, n), 256, B, rounds);
+    be.launch("k_jpd_cleanup", k_jpd_cleanup, dim3(gint, n), 64, B, rounds);
+    be.launch("k_jpd_blkscan", k_jpd_blkscan, dim3(n), 256, B);
+    be.launch("k_jpd_write", k_jpd_write, dim3(gsub, n), 256, B, rounds);
+    be.launch("k_jpd_dc", k_jpd_dc, dim3(3, n), 256, B);
+    be.launch("k_jpd_idct", k_jpd_idct, dim3(gblk, n), 64, B);
+    be.launch("k_jpd_color", k_jpd_color, dim3(gpix, n), 256, B, static_cast<uint8_t *>(out.data), out.step, out.frame_stride, out.rows,
+              out.cols, out.channels);
+    if (d_unsettled) be.copy(d_unsettled, B.stats, 2 * sizeof(unsigned long long));
+}
+
 }  // namespace
 
 UWIP_API int uwip_jpeg_info(const uint8_t *buf, size_t len, int32_t *rows, int32_t *cols, int32_t *channels)
@@ -593,13 +637,8 @@ UWIP_API int uwip_jpeg_decode(uwip_ctx *ctx, const uint8_t *const *h_streams, co
 {
     int rc = uwip_check_batch(ctx, out, 0);
     if (rc) return rc;
-    UWIP_REQUIRE(ctx, n >= 0 && n <= 65535, "at most 65535 frames per call");
-    UWIP_REQUIRE(ctx, out->frames == n, "the batch must hold one frame per stream");
-    if (n == 0) return UWIP_OK;
-    UWIP_REQUIRE(ctx, h_streams != nullptr && h_sizes != nullptr && d_status != nullptr, "null argument");
-    UWIP_REQUIRE(ctx, out->rows >= 1 && out->cols >= 1, "empty frame");
-    for (int f = 0; f < n; ++f) UWIP_REQUIRE(ctx, h_streams[f] != nullptr || h_sizes[f] == 0, "null stream");
-    for (int f = 0; f < n; ++f) UWIP_REQUIRE(ctx, h_sizes[f] < ((size_t)1 << 28), "a stream of 256 MiB or more");
+    rc = uwip_check_streams(ctx, h_streams, h_sizes, n, out, d_status);
+    if (rc || n == 0) return rc;
     const int rounds = rounds_of(opts ? opts->sync_rounds : -1);
 
     // The page-locked staging buffer holds the descriptors, then the segments.  It is free again once the previous call's
@@ -628,90 +667,19 @@ UWIP_API int uwip_jpeg_decode(uwip_ctx *ctx, const uint8_t *const *h_streams, co
     UWIP_REQUIRE(ctx, !pl.too_large, "batch too large for one call");
 
     uint8_t *d_in = static_cast<uint8_t *>(uwip_ws(ctx, "jpegdec.in", in_bytes));
-    uint8_t *ubuf = static_cast<uint8_t *>(uwip_ws(ctx, "jpegdec.unstuffed", pl.ubuf_bytes + 16));
-    // per interval: istart, isub, ifirst; per subsequence: exit0, exit1, entry (64-bit), cnt, sblk, sint; then the statistics
-    const size_t ni = pl.nintv + 1, ns = pl.nsub + 1;
-    uint64_t *meta = static_cast<uint64_t *>(uwip_ws(ctx, "jpegdec.meta", ns * 3 * 8 + 16 + ns * 3 * 4 + ni * 3 * 4));
-    int16_t *coef = static_cast<int16_t *>(uwip_ws(ctx, "jpegdec.coef", (pl.nblk + 1) * 64 * sizeof(int16_t)));
-    uint8_t *planes = static_cast<uint8_t *>(uwip_ws(ctx, "jpegdec.planes", pl.plane_bytes + 16));
-    int32_t *err = static_cast<int32_t *>(uwip_ws(ctx, "jpegdec.err", (size_t)n * sizeof(int32_t)));
-    if (!d_in || !ubuf || !meta || !coef || !planes || !err) return UWIP_ERR_NOMEM;
-
+    if (!d_in) return UWIP_ERR_NOMEM;
     for (int f = 0; f < n; ++f)
         if (fr[f].status == 0 && fr[f].seg_len) std::memcpy(h_in + hdr + fr[f].seg_off, h_streams[f] + seg[f], fr[f].seg_len);
     UWIP_HIP(ctx, hipMemcpyAsync(d_in, h_in, hdr + pl.src_bytes, hipMemcpyHostToDevice, ctx->stream));
     UWIP_HIP(ctx, hipEventRecord(ctx->jpd_ev, ctx->stream));
 
-    DecBufs B;
-    B.fr = reinterpret_cast<const DecFrame *>(d_in);
-    B.src = d_in + hdr;
-    B.ubuf = ubuf;
-    B.exit0 = meta; B.exit1 = B.exit0 + ns; B.entry = B.exit1 + ns;
-    B.stats = reinterpret_cast<unsigned long long *>(B.entry + ns);
-    B.cnt = reinterpret_cast<uint32_t *>(B.stats + 2); B.sblk = B.cnt + ns; B.sint = B.sblk + ns;
-    B.istart = B.sint + ns; B.isub = B.istart + ni; B.ifirst = B.isub + ni;
-    B.coef = coef; B.planes = planes; B.status = d_status; B.err = err;
-    UWIP_HIP(ctx, hipMemsetAsync(err, 0, (size_t)n * sizeof(int32_t), ctx->stream));
-    UWIP_HIP(ctx, hipMemsetAsync(B.stats, 0, 16, ctx->stream));
-    UWIP_HIP(ctx, hipMemsetAsync(B.ifirst, 0xFF, ni * 4, ctx->stream));
-    UWIP_HIP(ctx, hipMemsetAsync(coef, 0, (pl.nblk + 1) * 64 * sizeof(int16_t), ctx->stream));
-
-    const unsigned gsub = uwip_cdiv(pl.max_sub ? pl.max_sub : 1, 256), gint = uwip_cdiv(pl.max_int ? pl.max_int : 1, 64);
-    const unsigned gblk = uwip_cdiv(pl.max_blk ? pl.max_blk : 1, 64), gpix = uwip_cdiv((size_t)out->rows * out->cols, 256);
-    {
-        uwip_kscope ks(ctx, "k_jpd_unstuff");
-        k_jpd_unstuff<<<n, 256, 0, ctx->stream>>>(B);
-    }
-    for (int r = 0; r <= rounds; ++r) {
-        uwip_kscope ks(ctx, r ? "k_jpd_round_sync" : "k_jpd_round");
-        k_jpd_round<<<dim3(gsub, n), 256, 0, ctx->stream>>>(B, r);
-    }
-    {
-        uwip_kscope ks(ctx, "k_jpd_check");
-        k_jpd_check<<<dim3(gsub, n), 256, 0, ctx->stream>>>(B, rounds);
-    }
-    {
-        uwip_kscope ks(ctx, "k_jpd_cleanup");
-        k_jpd_cleanup<<<dim3(gint, n), 64, 0, ctx->stream>>>(B, rounds);
-    }
-    {
-        uwip_kscope ks(ctx, "k_jpd_blkscan");
-        k_jpd_blkscan<<<n, 256, 0, ctx->stream>>>(B);
-    }
-    {
-        uwip_kscope ks(ctx, "k_jpd_write");
-        k_jpd_write<<<dim3(gsub, n), 256, 0, ctx->stream>>>(B, rounds);
-    }
-    {
-        uwip_kscope ks(ctx, "k_jpd_dc");
-        k_jpd_dc<<<dim3(3, n), 256, 0, ctx->stream>>>(B);
-    }
-    {
-        uwip_kscope ks(ctx, "k_jpd_idct");
-        k_jpd_idct<<<dim3(gblk, n), 64, 0, ctx->stream>>>(B);
-    }
-    {
-        uwip_kscope ks(ctx, "k_jpd_color");
-        k_jpd_color<<<dim3(gpix, n), 256, 0, ctx->stream>>>(B, static_cast<uint8_t *>(out->data), out->step, out->frame_stride, out->rows,
-                                                            out->cols, out->channels);
-    }
-    if (opts && opts->d_unsettled)
-        UWIP_HIP(ctx, hipMemcpyAsync(opts->d_unsettled, B.stats, 16, hipMemcpyDeviceToDevice, ctx->stream));
-    UWIP_HIP(ctx, hipGetLastError());
-    return UWIP_OK;
+    uwip_device dev(ctx);
+    decode_sequence(dev, reinterpret_cast<const DecFrame *>(d_in), d_in + hdr, pl, n, rounds, *out, d_status, opts ? opts->d_unsettled : nullptr);
+    return dev.finish();
 }
 
 UWIP_API int uwip_jpeg_decode_host(uwip_ctx *ctx, const uint8_t *const *h_streams, const size_t *h_sizes, int n, const uwip_batch_u8 *out,
                                    const uwip_jpeg_decode_opts *opts, int32_t *h_status)
 {
-    if (int rc = uwip_enter(ctx)) return rc;
-    UWIP_REQUIRE(ctx, n >= 0 && (h_status != nullptr || n == 0), "null status");
-    if (n == 0) return UWIP_OK;
-    int32_t *d_status = static_cast<int32_t *>(uwip_ws(ctx, "jpegdec.status", (size_t)n * sizeof(int32_t)));
-    if (!d_status) return UWIP_ERR_NOMEM;
-    int rc = uwip_jpeg_decode(ctx, h_streams, h_sizes, n, out, opts, d_status);
-    if (rc) return rc;
-    UWIP_HIP(ctx, hipMemcpyAsync(h_status, d_status, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
-    UWIP_HIP(ctx, uwip_stream_wait(ctx));
-    return UWIP_OK;
+    return uwip_decode_to_host(ctx, h_streams, h_sizes, n, out, opts, h_status, uwip_jpeg_decode, "jpegdec.status");
 }

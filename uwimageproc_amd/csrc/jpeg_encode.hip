@@ -78,7 +78,7 @@ __device__ __forceinline__ int block_prev(const Geo &g, int b)
 }
 
 __global__ __launch_bounds__(256) void k_jpeg_transform(const uint8_t *__restrict__ img, Geo g, const JpegConst *__restrict__ cst,
-                                                        int16_t *__restrict__ coef, const int32_t *__restrict__ nsel = nullptr)
+                                                        int16_t *__restrict__ coef, const int32_t *__restrict__ nsel)
 {
     __shared__ int32_t s_qv[2][64];
     if (nsel && (int)blockIdx.y >= *nsel) return;                        // uniform over the workgroup, ahead of every barrier
@@ -194,7 +194,7 @@ __device__ __forceinline__ void code_block(const int16_t *__restrict__ coef, con
 
 __global__ __launch_bounds__(kBitsWG) void k_jpeg_bits(const int16_t *__restrict__ coef, Geo g, const JpegHuff *__restrict__ huff,
                                                        uint32_t *__restrict__ blkoff, uint32_t *__restrict__ wgsum, int nwg,
-                                                       const int32_t *__restrict__ nsel = nullptr)
+                                                       const int32_t *__restrict__ nsel)
 {
     __shared__ uint32_t s_dc[2][16], s_ac[2][256], s_scan[8];
     if (nsel && (int)blockIdx.y >= *nsel) return;
@@ -225,7 +225,7 @@ __device__ uint64_t scan_excl_u64(const uint32_t *__restrict__ in, uint64_t *__r
 }
 
 __global__ __launch_bounds__(256) void k_jpeg_scan_bits(const uint32_t *__restrict__ wgsum, uint64_t *__restrict__ wgbase,
-                                                        uint64_t *__restrict__ totbits, int nwg, const int32_t *__restrict__ nsel = nullptr)
+                                                        uint64_t *__restrict__ totbits, int nwg, const int32_t *__restrict__ nsel)
 {
     __shared__ uint32_t s_scan[8];
     const int f = blockIdx.x;
@@ -253,7 +253,7 @@ __device__ __forceinline__ bool stores(uint64_t totbits, uint32_t hdr_len, size_
 
 // zero the words two emit workgroups share, ahead of their atomicOr
 __global__ void k_jpeg_zero_shared(Geo g, Offs o, const JpegConst *__restrict__ cst, size_t slot_bytes, uint32_t *__restrict__ ubuf,
-                                   size_t ustride, int nwg_emit, const int32_t *__restrict__ nsel = nullptr)
+                                   size_t ustride, int nwg_emit, const int32_t *__restrict__ nsel)
 {
     const int w = blockIdx.x * blockDim.x + threadIdx.x, f = blockIdx.y;
     if (w < 1 || w >= nwg_emit) return;
@@ -266,7 +266,7 @@ __global__ void k_jpeg_zero_shared(Geo g, Offs o, const JpegConst *__restrict__ 
 __global__ __launch_bounds__(kEmitWG) void k_jpeg_emit(const int16_t *__restrict__ coef, Geo g, const JpegHuff *__restrict__ huff, Offs o,
                                                        const JpegConst *__restrict__ cst, size_t slot_bytes,
                                                        uint32_t *__restrict__ ubuf, size_t ustride, uint32_t *__restrict__ ffemit,
-                                                       uint32_t *__restrict__ notff, int nwg_emit, const int32_t *__restrict__ nsel = nullptr)
+                                                       uint32_t *__restrict__ notff, int nwg_emit, const int32_t *__restrict__ nsel)
 {
     __shared__ uint32_t s_dc[2][16], s_ac[2][256], s_win[kWinWords], s_cnt;
     if (nsel && (int)blockIdx.y >= *nsel) return;
@@ -347,7 +347,7 @@ __device__ __forceinline__ uint32_t chunk_ff(const uint32_t *__restrict__ ubuf_f
 
 __global__ __launch_bounds__(256) void k_jpeg_ffcount(const uint32_t *__restrict__ ubuf, size_t ustride, const uint64_t *__restrict__ totbits,
                                                       const JpegConst *__restrict__ cst, size_t slot_bytes, uint32_t *__restrict__ chunkcnt,
-                                                      int nchunk, const int32_t *__restrict__ nsel = nullptr)
+                                                      int nchunk, const int32_t *__restrict__ nsel)
 {
     __shared__ uint32_t s_scan[8];
     const int c = blockIdx.x, f = blockIdx.y;
@@ -367,7 +367,7 @@ __global__ __launch_bounds__(256) void k_jpeg_ffcount(const uint32_t *__restrict
 __global__ __launch_bounds__(256) void k_jpeg_finish(const uint32_t *__restrict__ chunkcnt, uint64_t *__restrict__ chunkbase, int nchunk, Geo g,
                                                      Offs o, const JpegConst *__restrict__ cst, const uint32_t *__restrict__ ffemit,
                                                      const uint32_t *__restrict__ notff, int nwg_emit, int64_t *__restrict__ needed,
-                                                     const int32_t *__restrict__ nsel = nullptr)
+                                                     const int32_t *__restrict__ nsel)
 {
     __shared__ uint32_t s_scan[8];
     const int f = blockIdx.x;
@@ -384,7 +384,7 @@ __global__ __launch_bounds__(256) void k_jpeg_finish(const uint32_t *__restrict_
 __global__ __launch_bounds__(256) void k_jpeg_assemble(const uint32_t *__restrict__ ubuf, size_t ustride, const uint64_t *__restrict__ totbits,
                                                        const uint64_t *__restrict__ chunkbase, int nchunk, const JpegConst *__restrict__ cst,
                                                        const int64_t *__restrict__ needed, uint8_t *__restrict__ streams, size_t slot_bytes,
-                                                       int64_t *__restrict__ sizes, const int32_t *__restrict__ nsel = nullptr)
+                                                       int64_t *__restrict__ sizes, const int32_t *__restrict__ nsel)
 {
     __shared__ uint32_t s_scan[8];
     const int c = blockIdx.x, f = blockIdx.y;
@@ -442,6 +442,62 @@ int blocks_of(int rows, int cols, int nc, int *mcux_out)
     return mcux * mcuy * (nc == 3 ? 6 : 1);
 }
 
+// the Annex K tables as the kernels read them
+void build_huff(JpegHuff &h)
+{
+    using namespace uwip_jpeg;
+    std::memset(&h, 0, sizeof h);
+    uint32_t t[256];
+    build_codes(DC_LUM_BITS, DC_VALS, t); std::memcpy(h.dc[0], t, sizeof h.dc[0]);
+    build_codes(DC_CHR_BITS, DC_VALS, t); std::memcpy(h.dc[1], t, sizeof h.dc[1]);
+    build_codes(AC_LUM_BITS, AC_LUM_VALS, h.ac[0]);
+    build_codes(AC_CHR_BITS, AC_CHR_VALS, h.ac[1]);
+}
+
+// uwip_jpeg_encode_dev behind its argument checks and table caches, on either back end (uwip_device; the host threads of
+// tests/hip_on_host.hpp): the working arrays and every launch.  huff / cst: the tables where the kernels read them; d_count:
+// null, or the device's frame count.
+template <class BE>
+void encode_sequence(BE &be, const uint8_t *img, const Geo &g, int F, const JpegHuff *huff, const JpegConst *cst, uint8_t *d_streams,
+                     size_t slot_bytes, int64_t *d_sizes, const int32_t *d_count)
+{
+    using dim3 = typename BE::dim3;                           // HIP's on the device, its stand-in on host threads
+    const int nwg_bits = (int)uwip_cdiv((size_t)g.nblk, kBitsWG), nwg_emit = (int)uwip_cdiv((size_t)g.nblk, kEmitWG);
+    // the unstuffed stream of a frame is kept only when it fits the slot, so the slot bounds its buffer as well
+    const size_t ubound = ((size_t)g.nblk * kMaxBlockBits + 7) / 8;
+    const size_t ucap = slot_bytes < ubound ? slot_bytes : ubound;
+    const size_t ustride = ((ucap + 15) / 16) * 4 + 8;                   // words; a multiple of 4: uint4 loads
+    const int nchunk = ucap ? (int)uwip_cdiv(ucap, kChunk) : 1;
+    const size_t nf = (size_t)F;
+
+    int16_t *coef = be.template array<int16_t>("jpeg.coef", nf * g.nblk * 64);
+    uint32_t *ubuf = be.template array<uint32_t>("jpeg.unstuffed", nf * ustride);
+    uint32_t *blkoff = be.template array<uint32_t>("jpeg.blkoff", nf * g.nblk);
+    uint32_t *wgsum = be.template array<uint32_t>("jpeg.wgsum", nf * nwg_bits);
+    uint64_t *wgbase = be.template array<uint64_t>("jpeg.wgbase", nf * nwg_bits);
+    uint64_t *totbits = be.template array<uint64_t>("jpeg.totbits", nf);
+    uint32_t *chunkcnt = be.template array<uint32_t>("jpeg.chunkcnt", nf * nchunk);
+    uint64_t *chunkbase = be.template array<uint64_t>("jpeg.chunkbase", nf * nchunk);
+    int64_t *needed = be.template array<int64_t>("jpeg.needed", nf);
+    uint32_t *ffemit = be.template array<uint32_t>("jpeg.ffemit", nf);
+    uint32_t *notff = be.template array<uint32_t>("jpeg.notff", nf * (nwg_emit + 1));
+    be.fill(ffemit, 0, nf * sizeof(uint32_t));
+    be.fill(notff, 0, nf * (nwg_emit + 1) * sizeof(uint32_t));
+
+    const Offs o{blkoff, wgbase, totbits, nwg_bits};
+    be.launch("k_jpeg_transform", k_jpeg_transform, dim3(nwg_bits, F), 256, img, g, cst, coef, d_count);
+    be.launch("k_jpeg_bits", k_jpeg_bits, dim3(nwg_bits, F), kBitsWG, coef, g, huff, blkoff, wgsum, nwg_bits, d_count);
+    be.launch("k_jpeg_scan_bits", k_jpeg_scan_bits, dim3(F), 256, wgsum, wgbase, totbits, nwg_bits, d_count);
+    be.launch("k_jpeg_zero_shared", k_jpeg_zero_shared, dim3(uwip_cdiv((size_t)nwg_emit, 256), F), 256, g, o, cst, slot_bytes, ubuf, ustride,
+              nwg_emit, d_count);
+    be.launch("k_jpeg_emit", k_jpeg_emit, dim3(nwg_emit, F), kEmitWG, coef, g, huff, o, cst, slot_bytes, ubuf, ustride, ffemit, notff, nwg_emit,
+              d_count);
+    be.launch("k_jpeg_ffcount", k_jpeg_ffcount, dim3(nchunk, F), 256, ubuf, ustride, totbits, cst, slot_bytes, chunkcnt, nchunk, d_count);
+    be.launch("k_jpeg_finish", k_jpeg_finish, dim3(F), 256, chunkcnt, chunkbase, nchunk, g, o, cst, ffemit, notff, nwg_emit, needed, d_count);
+    be.launch("k_jpeg_assemble", k_jpeg_assemble, dim3(nchunk, F), 256, ubuf, ustride, totbits, chunkbase, nchunk, cst, needed, d_streams,
+              slot_bytes, d_sizes, d_count);
+}
+
 }  // namespace
 
 UWIP_API size_t uwip_jpeg_bound(int rows, int cols, int channels)
@@ -478,14 +534,8 @@ int uwip_jpeg_encode_dev(uwip_ctx *ctx, const uwip_batch_u8 *frames, int quality
 
     const void *d_huff = uwip_table_find(ctx, "jpeg.huff", nullptr);
     if (!d_huff) {
-        using namespace uwip_jpeg;
         std::vector<JpegHuff> h(1);
-        std::memset(h.data(), 0, sizeof(JpegHuff));
-        uint32_t t[256];
-        build_codes(DC_LUM_BITS, DC_VALS, t); std::memcpy(h[0].dc[0], t, sizeof h[0].dc[0]);
-        build_codes(DC_CHR_BITS, DC_VALS, t); std::memcpy(h[0].dc[1], t, sizeof h[0].dc[1]);
-        build_codes(AC_LUM_BITS, AC_LUM_VALS, h[0].ac[0]);
-        build_codes(AC_CHR_BITS, AC_CHR_VALS, h[0].ac[1]);
+        build_huff(h[0]);
         d_huff = uwip_table_put(ctx, "jpeg.huff", h.data(), sizeof(JpegHuff));
         if (!d_huff) return UWIP_ERR_HIP;
     }
@@ -502,88 +552,13 @@ int uwip_jpeg_encode_dev(uwip_ctx *ctx, const uwip_batch_u8 *frames, int quality
     const JpegHuff *huff = static_cast<const JpegHuff *>(d_huff);
     const JpegConst *cst = static_cast<const JpegConst *>(d_cst);
 
-    const int nwg_bits = (int)uwip_cdiv((size_t)g.nblk, kBitsWG), nwg_emit = (int)uwip_cdiv((size_t)g.nblk, kEmitWG);
-    // the unstuffed stream of a frame is kept only when it fits the slot, so the slot bounds its buffer as well
-    const size_t ubound = ((size_t)g.nblk * kMaxBlockBits + 7) / 8;
-    const size_t ucap = slot_bytes < ubound ? slot_bytes : ubound;
-    const size_t ustride = ((ucap + 15) / 16) * 4 + 8;                   // words; a multiple of 4: uint4 loads
-    const int nchunk = ucap ? (int)uwip_cdiv(ucap, kChunk) : 1;
-
-    int16_t *coef = static_cast<int16_t *>(uwip_ws(ctx, "jpeg.coef", (size_t)F * g.nblk * 64 * sizeof(int16_t)));
-    uint32_t *ubuf = static_cast<uint32_t *>(uwip_ws(ctx, "jpeg.unstuffed", (size_t)F * ustride * sizeof(uint32_t)));
-    uint32_t *blkoff = static_cast<uint32_t *>(uwip_ws(ctx, "jpeg.blkoff", (size_t)F * g.nblk * sizeof(uint32_t)));
-    // the small per-frame arrays share one buffer: 64-bit ones first
-    const size_t n64 = (size_t)F * nwg_bits + F + (size_t)F * nchunk + F;
-    const size_t n32 = (size_t)F * nwg_bits + (size_t)F * nchunk + F + (size_t)F * (nwg_emit + 1);
-    uint64_t *meta = static_cast<uint64_t *>(uwip_ws(ctx, "jpeg.meta", n64 * 8 + n32 * 4));
-    if (!coef || !ubuf || !blkoff || !meta) return UWIP_ERR_NOMEM;
-    uint64_t *wgbase = meta, *totbits = wgbase + (size_t)F * nwg_bits, *chunkbase = totbits + F;
-    int64_t *needed = reinterpret_cast<int64_t *>(chunkbase + (size_t)F * nchunk);
-    uint32_t *wgsum = reinterpret_cast<uint32_t *>(needed + F), *chunkcnt = wgsum + (size_t)F * nwg_bits;
-    uint32_t *ffemit = chunkcnt + (size_t)F * nchunk, *notff = ffemit + F;
-    UWIP_HIP(ctx, hipMemsetAsync(ffemit, 0, ((size_t)F + (size_t)F * (nwg_emit + 1)) * sizeof(uint32_t), ctx->stream));
-
-    const Offs o{blkoff, wgbase, totbits, nwg_bits};
-    const uint8_t *img = static_cast<const uint8_t *>(frames->data);
-    {
-        uwip_kscope ks(ctx, "k_jpeg_transform");
-        k_jpeg_transform<<<dim3(nwg_bits, F), 256, 0, ctx->stream>>>(img, g, cst, coef, d_count);
-    }
-    {
-        uwip_kscope ks(ctx, "k_jpeg_bits");
-        k_jpeg_bits<<<dim3(nwg_bits, F), kBitsWG, 0, ctx->stream>>>(coef, g, huff, blkoff, wgsum, nwg_bits, d_count);
-    }
-    {
-        uwip_kscope ks(ctx, "k_jpeg_scan_bits");
-        k_jpeg_scan_bits<<<F, 256, 0, ctx->stream>>>(wgsum, wgbase, totbits, nwg_bits, d_count);
-    }
-    {
-        uwip_kscope ks(ctx, "k_jpeg_zero_shared");
-        k_jpeg_zero_shared<<<dim3(uwip_cdiv((size_t)nwg_emit, 256), F), 256, 0, ctx->stream>>>(g, o, cst, slot_bytes, ubuf, ustride,
-                                                                                               nwg_emit, d_count);
-    }
-    {
-        uwip_kscope ks(ctx, "k_jpeg_emit");
-        k_jpeg_emit<<<dim3(nwg_emit, F), kEmitWG, 0, ctx->stream>>>(coef, g, huff, o, cst, slot_bytes, ubuf, ustride, ffemit, notff,
-                                                                    nwg_emit, d_count);
-    }
-    {
-        uwip_kscope ks(ctx, "k_jpeg_ffcount");
-        k_jpeg_ffcount<<<dim3(nchunk, F), 256, 0, ctx->stream>>>(ubuf, ustride, totbits, cst, slot_bytes, chunkcnt, nchunk, d_count);
-    }
-    {
-        uwip_kscope ks(ctx, "k_jpeg_finish");
-        k_jpeg_finish<<<F, 256, 0, ctx->stream>>>(chunkcnt, chunkbase, nchunk, g, o, cst, ffemit, notff, nwg_emit, needed, d_count);
-    }
-    {
-        uwip_kscope ks(ctx, "k_jpeg_assemble");
-        k_jpeg_assemble<<<dim3(nchunk, F), 256, 0, ctx->stream>>>(ubuf, ustride, totbits, chunkbase, nchunk, cst, needed, d_streams,
-                                                                  slot_bytes, d_sizes, d_count);
-    }
-    UWIP_HIP(ctx, hipGetLastError());
-    return UWIP_OK;
+    uwip_device dev(ctx);
+    encode_sequence(dev, static_cast<const uint8_t *>(frames->data), g, F, huff, cst, d_streams, slot_bytes, d_sizes, d_count);
+    return dev.finish();
 }
 
 UWIP_API int uwip_jpeg_encode_host(uwip_ctx *ctx, const uwip_batch_u8 *frames, int quality, uint8_t *h_streams, size_t slot_bytes,
                                    int64_t *h_sizes)
 {
-    int rc = uwip_check_batch(ctx, frames, 0);
-    if (rc) return rc;
-    const int F = frames->frames;
-    if (F == 0) return UWIP_OK;
-    UWIP_REQUIRE(ctx, h_sizes != nullptr, "null sizes");
-    UWIP_REQUIRE(ctx, h_streams != nullptr || slot_bytes == 0, "null streams");
-    uint8_t *d_out = static_cast<uint8_t *>(uwip_ws(ctx, "jpeg.streams", (size_t)F * slot_bytes + 16));
-    int64_t *d_sizes = static_cast<int64_t *>(uwip_ws(ctx, "jpeg.sizes", (size_t)F * sizeof(int64_t)));
-    if (!d_out || !d_sizes) return UWIP_ERR_NOMEM;
-    rc = uwip_jpeg_encode(ctx, frames, quality, d_out, slot_bytes, d_sizes);
-    if (rc) return rc;
-    UWIP_HIP(ctx, hipMemcpyAsync(h_sizes, d_sizes, (size_t)F * sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
-    UWIP_HIP(ctx, uwip_stream_wait(ctx));
-    for (int f = 0; f < F; ++f)
-        if (h_sizes[f] > 0)
-            UWIP_HIP(ctx, hipMemcpyAsync(h_streams + (size_t)f * slot_bytes, d_out + (size_t)f * slot_bytes, (size_t)h_sizes[f],
-                                         hipMemcpyDeviceToHost, ctx->stream));
-    UWIP_HIP(ctx, uwip_stream_wait(ctx));
-    return UWIP_OK;
+    return uwip_encode_to_host(ctx, frames, quality, h_streams, slot_bytes, h_sizes, uwip_jpeg_encode, "jpeg.streams", "jpeg.sizes");
 }

@@ -465,14 +465,69 @@ void spec_plan_frame(PFrame &d, uint32_t chunk_bytes, size_t &nslots, uint32_t &
     nslots += d.nchunks + kRepairs;
     maxslots = std::max(maxslots, d.nchunks + (uint32_t)kRepairs);
 }
-size_t spec_meta_bytes(size_t n, size_t nslots) { return n * sizeof(PSpecFrame) + nslots * (sizeof(PChunk) + 4) + 16; }
+// the records of the found block starts share one buffer: a PSpecFrame per frame, then per chunk record a PChunk, then its place
+// in the chain's order, and 16 spare bytes.  The one statement of that layout: the byte count and the pointers both come from it
+struct SpecLayout {
+    size_t chunk, order, bytes;
+    SpecLayout(size_t n, size_t nslots)
+        : chunk(n * sizeof(PSpecFrame)), order(chunk + nslots * sizeof(PChunk)), bytes(order + nslots * sizeof(uint32_t) + 16) {}
+};
+size_t spec_meta_bytes(size_t n, size_t nslots) { return SpecLayout(n, nslots).bytes; }
 void spec_bind(PBufs &B, void *meta, void *sym, size_t n, size_t nslots, uint32_t chunk_bytes)
 {
-    B.spec = static_cast<PSpecFrame *>(meta);
-    B.chunk = reinterpret_cast<PChunk *>(B.spec + n);
-    B.order = reinterpret_cast<uint32_t *>(B.chunk + nslots);
+    const SpecLayout l(n, nslots);
+    uint8_t *m = static_cast<uint8_t *>(meta);
+    B.spec = reinterpret_cast<PSpecFrame *>(m);
+    B.chunk = reinterpret_cast<PChunk *>(m + l.chunk);
+    B.order = reinterpret_cast<uint32_t *>(m + l.order);
     B.sym = static_cast<uint16_t *>(sym);
     B.chunk_bits = chunk_bytes * 8u;
+}
+
+// uwip_png_decode behind the upload, on either back end (uwip_device; the host threads of tests/hip_on_host.hpp): the working
+// arrays, their first values and every launch of the three modes.  fr / seg / src: the descriptors, the nsegtot segments of
+// launch 0 and the zlib streams, where the kernels read them; nslots / maxslots: the chunk records of the found block starts
+// over the batch and the most a frame has (spec_plan_frame), 0 where no frame takes that path.
+template <class BE>
+void decode_sequence(BE &be, const PFrame *fr, const PSeg *seg, const uint8_t *src, size_t nsegtot, size_t nslots, uint32_t maxslots,
+                     uint32_t chunk_bytes, int n, const uwip_batch_u8 &out, int32_t *d_status, void *d_counts)
+{
+    using dim3 = typename BE::dim3;                           // HIP's on the device, its stand-in on host threads
+    const size_t wsb = ws_bytes(out.rows, out.cols);
+    PGeoD g;
+    g.rows = out.rows; g.cols = out.cols; g.ws_stride = (uint32_t)wsb; g.npieces = (uint32_t)((wsb + kChunk - 1) / kChunk);
+    PBufs B;
+    B.fr = fr; B.seg = seg; B.src = src; B.status = d_status;
+    B.nsegtot = (uint32_t)nsegtot; B.nframes = (uint32_t)n;
+    B.ws = be.template array<uint8_t>("pngdec.inflated", (size_t)n * wsb + 16);
+    B.counts = be.template array<unsigned long long>("pngdec.counts", 3);
+    B.res = be.template array<PRes>("pngdec.res", nsegtot + n);
+    B.asum = be.template array<uint32_t>("pngdec.asum", (size_t)n * g.npieces * 2);
+    if (nslots) {                                             // only where the found block starts are used
+        spec_bind(B, be.template array<uint8_t>("pngdec.chunks", spec_meta_bytes((size_t)n, nslots)),
+                  be.template array<uint16_t>("pngdec.symbols", (size_t)n * wsb), (size_t)n, nslots, chunk_bytes);
+    }
+    be.fill(B.counts, 0, 3 * sizeof(unsigned long long));
+    if (nsegtot) be.launch("k_pngd_inflate_segments", k_pngd_inflate, dim3((unsigned)nsegtot), 64, B, g, 0);
+    if (nslots) {
+        const unsigned nb = uwip_cdiv((size_t)n, 64);
+        be.launch("k_pngs_begin", k_pngs_begin, dim3(nb), 64, B);
+        be.launch("k_pngs_measure", k_pngs_measure, dim3(maxslots - kRepairs, n), 64, B, g, 0);
+        be.launch("k_pngs_verify", k_pngs_verify, dim3(nb), 64, B, g);
+        for (int r = 0; r < kRepairs; ++r) {
+            be.launch("k_pngs_measure_repair", k_pngs_measure, dim3(1, n), 64, B, g, 1);
+            be.launch("k_pngs_verify", k_pngs_verify, dim3(nb), 64, B, g);
+        }
+        be.launch("k_pngs_write", k_pngs_write, dim3(maxslots, n), 64, B, g);
+        be.launch("k_pngs_window", k_pngs_window, dim3(n), 256, B, g);
+        be.launch("k_pngs_resolve", k_pngs_resolve, dim3(maxslots, n), 256, B, g);
+    }
+    be.launch("k_pngd_inflate", k_pngd_inflate, dim3(n), 64, B, g, 1);
+    be.launch("k_pngd_adler", k_pngd_adler, dim3(g.npieces, n), 256, B, g);
+    be.launch("k_pngd_unfilter", k_pngd_unfilter, dim3(n), 64, B, g);
+    be.launch("k_pngd_color", k_pngd_color, dim3(uwip_cdiv((size_t)out.rows * out.cols, 256), n), 256, B, g, static_cast<uint8_t *>(out.data),
+              out.step, out.frame_stride, out.channels);
+    if (d_counts) be.copy(d_counts, B.counts, 3 * sizeof(unsigned long long));
 }
 
 }  // namespace
@@ -498,15 +553,10 @@ UWIP_API int uwip_png_decode(uwip_ctx *ctx, const uint8_t *const *h_streams, con
     }
     int rc = uwip_check_batch(ctx, out, 0);
     if (rc) return rc;
-    UWIP_REQUIRE(ctx, n >= 0 && n <= 65535, "at most 65535 frames per call");
-    UWIP_REQUIRE(ctx, out->frames == n, "the batch must hold one frame per stream");
     UWIP_REQUIRE(ctx, opts_ok, "segmented must be -1, 0, 1 or 2; chunk_bytes 0, or 256 .. 1 MiB with segmented 2");
-    if (n == 0) return UWIP_OK;
-    UWIP_REQUIRE(ctx, h_streams != nullptr && h_sizes != nullptr && d_status != nullptr, "null argument");
-    UWIP_REQUIRE(ctx, out->rows >= 1 && out->cols >= 1, "empty frame");
+    rc = uwip_check_streams(ctx, h_streams, h_sizes, n, out, d_status);
+    if (rc || n == 0) return rc;
     UWIP_REQUIRE(ctx, out->rows <= 65535 && out->cols <= 65535, "at most 65535 rows / columns");
-    for (int f = 0; f < n; ++f) UWIP_REQUIRE(ctx, h_streams[f] != nullptr || h_sizes[f] == 0, "null stream");
-    for (int f = 0; f < n; ++f) UWIP_REQUIRE(ctx, h_sizes[f] < ((size_t)1 << 28), "a stream of 256 MiB or more");
     const int segmented = mode < 0 ? 1 : mode;
     const uint32_t chunk_bytes = spec_chunk_bytes(asked);
     const size_t wsb = ws_bytes(out->rows, out->cols);
@@ -548,87 +598,20 @@ UWIP_API int uwip_png_decode(uwip_ctx *ctx, const uint8_t *const *h_streams, con
         if (fr[f].status == 0) uwip_pngd::gather(h_streams[f], parsed[f], h_in + hdr + fr[f].zoff);
     std::memset(h_in + hdr + pl.src_bytes, 0, 16);
 
-    const uint32_t npieces = (uint32_t)((wsb + kChunk - 1) / kChunk);
     uint8_t *d_in = static_cast<uint8_t *>(uwip_ws(ctx, "pngdec.in", in_bytes));
-    uint8_t *ws = static_cast<uint8_t *>(uwip_ws(ctx, "pngdec.inflated", (size_t)n * wsb + 16));
-    // the small arrays share one buffer: the counts, the results, the Adler sums
-    uint64_t *meta = static_cast<uint64_t *>(uwip_ws(ctx, "pngdec.meta", 32 + (nsegtot + n) * sizeof(PRes) + (size_t)n * npieces * 8));
-    if (!d_in || !ws || !meta) return UWIP_ERR_NOMEM;
-    void *spec_meta = nullptr, *spec_sym = nullptr;          // only where the found block starts are used
-    if (nslots) {
-        spec_meta = uwip_ws(ctx, "pngdec.chunks", spec_meta_bytes((size_t)n, nslots));
-        spec_sym = uwip_ws(ctx, "pngdec.symbols", ((size_t)n * wsb + 16) * 2);
-        if (!spec_meta || !spec_sym) return UWIP_ERR_NOMEM;
-    }
+    if (!d_in) return UWIP_ERR_NOMEM;
     UWIP_HIP(ctx, hipMemcpyAsync(d_in, h_in, in_bytes, hipMemcpyHostToDevice, ctx->stream));
     UWIP_HIP(ctx, hipEventRecord(ctx->pngd_ev, ctx->stream));
 
-    PBufs B;
-    B.fr = reinterpret_cast<const PFrame *>(d_in);
-    B.seg = reinterpret_cast<const PSeg *>(d_in + (size_t)n * sizeof(PFrame));
-    B.src = d_in + hdr;
-    B.ws = ws;
-    B.counts = reinterpret_cast<unsigned long long *>(meta);
-    B.res = reinterpret_cast<PRes *>(meta + 4);
-    B.asum = reinterpret_cast<uint32_t *>(B.res + nsegtot + n);
-    B.status = d_status;
-    B.nsegtot = (uint32_t)nsegtot; B.nframes = (uint32_t)n;
-    PGeoD g;
-    g.rows = out->rows; g.cols = out->cols; g.ws_stride = (uint32_t)wsb; g.npieces = npieces;
-    UWIP_HIP(ctx, hipMemsetAsync(meta, 0, 32, ctx->stream));
-    if (nsegtot) {
-        uwip_kscope ks(ctx, "k_pngd_inflate_segments");
-        k_pngd_inflate<<<(unsigned)nsegtot, 64, 0, ctx->stream>>>(B, g, 0);
-    }
-    if (nslots) {
-        spec_bind(B, spec_meta, spec_sym, (size_t)n, nslots, chunk_bytes);
-        const unsigned nb = uwip_cdiv((size_t)n, 64);
-        { uwip_kscope ks(ctx, "k_pngs_begin"); k_pngs_begin<<<nb, 64, 0, ctx->stream>>>(B); }
-        { uwip_kscope ks(ctx, "k_pngs_measure"); k_pngs_measure<<<dim3(maxslots - kRepairs, n), 64, 0, ctx->stream>>>(B, g, 0); }
-        { uwip_kscope ks(ctx, "k_pngs_verify"); k_pngs_verify<<<nb, 64, 0, ctx->stream>>>(B, g); }
-        for (int r = 0; r < kRepairs; ++r) {
-            { uwip_kscope ks(ctx, "k_pngs_measure_repair"); k_pngs_measure<<<dim3(1, n), 64, 0, ctx->stream>>>(B, g, 1); }
-            { uwip_kscope ks(ctx, "k_pngs_verify"); k_pngs_verify<<<nb, 64, 0, ctx->stream>>>(B, g); }
-        }
-        { uwip_kscope ks(ctx, "k_pngs_write"); k_pngs_write<<<dim3(maxslots, n), 64, 0, ctx->stream>>>(B, g); }
-        { uwip_kscope ks(ctx, "k_pngs_window"); k_pngs_window<<<n, 256, 0, ctx->stream>>>(B, g); }
-        { uwip_kscope ks(ctx, "k_pngs_resolve"); k_pngs_resolve<<<dim3(maxslots, n), 256, 0, ctx->stream>>>(B, g); }
-    }
-    {
-        uwip_kscope ks(ctx, "k_pngd_inflate");
-        k_pngd_inflate<<<n, 64, 0, ctx->stream>>>(B, g, 1);
-    }
-    {
-        uwip_kscope ks(ctx, "k_pngd_adler");
-        k_pngd_adler<<<dim3(npieces, n), 256, 0, ctx->stream>>>(B, g);
-    }
-    {
-        uwip_kscope ks(ctx, "k_pngd_unfilter");
-        k_pngd_unfilter<<<n, 64, 0, ctx->stream>>>(B, g);
-    }
-    {
-        uwip_kscope ks(ctx, "k_pngd_color");
-        k_pngd_color<<<dim3(uwip_cdiv((size_t)out->rows * out->cols, 256), n), 256, 0, ctx->stream>>>(
-            B, g, static_cast<uint8_t *>(out->data), out->step, out->frame_stride, out->channels);
-    }
-    if (opts && opts->d_counts)
-        UWIP_HIP(ctx, hipMemcpyAsync(opts->d_counts, B.counts, 24, hipMemcpyDeviceToDevice, ctx->stream));
-    UWIP_HIP(ctx, hipGetLastError());
-    return UWIP_OK;
+    uwip_device dev(ctx);
+    decode_sequence(dev, reinterpret_cast<const PFrame *>(d_in), reinterpret_cast<const PSeg *>(d_in + (size_t)n * sizeof(PFrame)), d_in + hdr,
+                    nsegtot, nslots, maxslots, chunk_bytes, n, *out, d_status, opts ? opts->d_counts : nullptr);
+    return dev.finish();
 }
 
 UWIP_API int uwip_png_decode_host(uwip_ctx *ctx, const uint8_t *const *h_streams, const size_t *h_sizes, int n, const uwip_batch_u8 *out,
                                   const uwip_png_decode_opts *opts, int32_t *h_status)
 {
     if (!ctx) return uwip_png_decode(ctx, h_streams, h_sizes, n, out, opts, nullptr);
-    if (int rc = uwip_enter(ctx)) return rc;
-    UWIP_REQUIRE(ctx, n >= 0 && (h_status != nullptr || n == 0), "null status");
-    if (n == 0) return UWIP_OK;
-    int32_t *d_status = static_cast<int32_t *>(uwip_ws(ctx, "pngdec.status", (size_t)n * sizeof(int32_t)));
-    if (!d_status) return UWIP_ERR_NOMEM;
-    int rc = uwip_png_decode(ctx, h_streams, h_sizes, n, out, opts, d_status);
-    if (rc) return rc;
-    UWIP_HIP(ctx, hipMemcpyAsync(h_status, d_status, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
-    UWIP_HIP(ctx, uwip_stream_wait(ctx));
-    return UWIP_OK;
+    return uwip_decode_to_host(ctx, h_streams, h_sizes, n, out, opts, h_status, uwip_png_decode, "pngdec.status");
 }

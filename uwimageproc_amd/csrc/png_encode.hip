@@ -37,7 +37,7 @@ struct PGeo {
 struct ChunkOut { uint32_t size, crc, a, b; };
 
 __global__ __launch_bounds__(256) void k_png_filter(const uint8_t *__restrict__ img, PGeo g, int filter, uint8_t *__restrict__ filt,
-                                                    const int32_t *__restrict__ nsel = nullptr)
+                                                    const int32_t *__restrict__ nsel)
 {
     __shared__ uint32_t s_scan[8];
     if (nsel && (int)blockIdx.y >= *nsel) return;                // uniform over the workgroup, ahead of every barrier
@@ -88,7 +88,7 @@ __device__ __forceinline__ void walk_tokens(const uint8_t *__restrict__ d, int n
 }
 
 __global__ __launch_bounds__(256) void k_png_deflate(const uint8_t *__restrict__ filt, PGeo g, uint8_t *__restrict__ stage,
-                                                     ChunkOut *__restrict__ cout, const int32_t *__restrict__ nsel = nullptr)
+                                                     ChunkOut *__restrict__ cout, const int32_t *__restrict__ nsel)
 {
     if (nsel && (int)blockIdx.y >= *nsel) return;
     __shared__ uint32_t s_freq[kNumLL], s_win[kWinWords], s_crc[256], s_tab[256], s_scan[8], s_nmatch;
@@ -196,7 +196,7 @@ __global__ __launch_bounds__(256) void k_png_deflate(const uint8_t *__restrict__
 // per frame: where each IDAT starts behind signature and IHDR, the stream length, the Adler-32
 __global__ __launch_bounds__(256) void k_png_finish(const ChunkOut *__restrict__ cout, PGeo g, uint64_t *__restrict__ coff,
                                                     int64_t *__restrict__ needed, uint32_t *__restrict__ adler,
-                                                    const int32_t *__restrict__ nsel = nullptr)
+                                                    const int32_t *__restrict__ nsel)
 {
     __shared__ uint32_t s_scan[8], s_tot[2];
     const int f = blockIdx.x, t = threadIdx.x;
@@ -231,7 +231,7 @@ __global__ __launch_bounds__(256) void k_png_assemble(const uint8_t *__restrict_
                                                       const uint64_t *__restrict__ coff, PGeo g, const uint8_t *__restrict__ head,
                                                       const int64_t *__restrict__ needed, const uint32_t *__restrict__ adler,
                                                       uint8_t *__restrict__ streams, size_t slot_bytes, int64_t *__restrict__ sizes,
-                                                      const int32_t *__restrict__ nsel = nullptr)
+                                                      const int32_t *__restrict__ nsel)
 {
     __shared__ uint8_t s_tail[kTailBytes];
     const int c = blockIdx.x, f = blockIdx.y, t = threadIdx.x;
@@ -262,6 +262,38 @@ __global__ __launch_bounds__(256) void k_png_assemble(const uint8_t *__restrict_
 bool png_geometry(int rows, int cols, int channels)
 {
     return rows >= 1 && cols >= 1 && rows <= 65535 && cols <= 65535 && (channels == 1 || channels == 3);
+}
+
+PGeo geometry_of(int rows, int cols, int nc, size_t step, size_t fs)
+{
+    PGeo g;
+    g.rows = rows; g.cols = cols; g.nc = nc; g.step = step; g.fs = fs;
+    g.total = filtered_bytes(rows, cols, nc);
+    g.nch = (int)chunks_of(g.total);
+    g.fstride = (size_t)g.nch * kChunk;
+    return g;
+}
+
+// uwip_png_encode_dev behind its argument checks and the cached head, on either back end (uwip_device; the host threads of
+// tests/hip_on_host.hpp): the working arrays and every launch.  head: signature and IHDR where the kernels read them; d_count:
+// null, or the device's frame count.
+template <class BE>
+void encode_sequence(BE &be, const uint8_t *img, const PGeo &g, int F, int filter, const uint8_t *head, uint8_t *d_streams, size_t slot_bytes,
+                     int64_t *d_sizes, const int32_t *d_count)
+{
+    using dim3 = typename BE::dim3;                           // HIP's on the device, its stand-in on host threads
+    const size_t nchunks = (size_t)F * g.nch;
+    uint8_t *filt = be.template array<uint8_t>("png.filtered", (size_t)F * g.fstride);
+    uint8_t *stage = be.template array<uint8_t>("png.staging", nchunks * kStageBytes);
+    ChunkOut *cout = be.template array<ChunkOut>("png.chunkout", nchunks);
+    uint64_t *coff = be.template array<uint64_t>("png.coff", nchunks);
+    int64_t *needed = be.template array<int64_t>("png.needed", (size_t)F);
+    uint32_t *adler = be.template array<uint32_t>("png.adler", (size_t)F);
+    be.launch("k_png_filter", k_png_filter, dim3(g.rows, F), 256, img, g, filter, filt, d_count);
+    be.launch("k_png_deflate", k_png_deflate, dim3(g.nch, F), 256, filt, g, stage, cout, d_count);
+    be.launch("k_png_finish", k_png_finish, dim3(F), 256, cout, g, coff, needed, adler, d_count);
+    be.launch("k_png_assemble", k_png_assemble, dim3(g.nch, F), 256, stage, cout, coff, g, head, needed, adler, d_streams, slot_bytes, d_sizes,
+              d_count);
 }
 
 }  // namespace
@@ -299,12 +331,7 @@ int uwip_png_encode_dev(uwip_ctx *ctx, const uwip_batch_u8 *frames, int filter, 
     UWIP_REQUIRE(ctx, d_sizes != nullptr, "null sizes");
     UWIP_REQUIRE(ctx, d_streams != nullptr || slot_bytes == 0, "null streams");
 
-    PGeo g;
-    g.rows = frames->rows; g.cols = frames->cols; g.nc = frames->channels;
-    g.step = frames->step; g.fs = frames->frame_stride;
-    g.total = filtered_bytes(g.rows, g.cols, g.nc);
-    g.nch = (int)chunks_of(g.total);
-    g.fstride = (size_t)g.nch * kChunk;
+    const PGeo g = geometry_of(frames->rows, frames->cols, frames->channels, frames->step, frames->frame_stride);
 
     char key[96];
     std::snprintf(key, sizeof key, "png.head.%dx%dx%d", g.rows, g.cols, g.nc);
@@ -315,60 +342,15 @@ int uwip_png_encode_dev(uwip_ctx *ctx, const uwip_batch_u8 *frames, int filter, 
         d_head = uwip_table_put(ctx, key, h, sizeof h);
         if (!d_head) return UWIP_ERR_HIP;
     }
-    const size_t nchunks = (size_t)F * g.nch;
-    uint8_t *filt = static_cast<uint8_t *>(uwip_ws(ctx, "png.filtered", (size_t)F * g.fstride));
-    uint8_t *stage = static_cast<uint8_t *>(uwip_ws(ctx, "png.staging", nchunks * kStageBytes));
-    // the small arrays share one buffer: 64-bit ones first
-    uint64_t *meta = static_cast<uint64_t *>(uwip_ws(ctx, "png.meta", nchunks * (8 + sizeof(ChunkOut)) + (size_t)F * 12));
-    if (!filt || !stage || !meta) return UWIP_ERR_NOMEM;
-    uint64_t *coff = meta;
-    int64_t *needed = reinterpret_cast<int64_t *>(coff + nchunks);
-    ChunkOut *cout = reinterpret_cast<ChunkOut *>(needed + F);
-    uint32_t *adler = reinterpret_cast<uint32_t *>(cout + nchunks);
-
-    const uint8_t *img = static_cast<const uint8_t *>(frames->data);
-    {
-        uwip_kscope ks(ctx, "k_png_filter");
-        k_png_filter<<<dim3(g.rows, F), 256, 0, ctx->stream>>>(img, g, filter, filt, d_count);
-    }
-    {
-        uwip_kscope ks(ctx, "k_png_deflate");
-        k_png_deflate<<<dim3(g.nch, F), 256, 0, ctx->stream>>>(filt, g, stage, cout, d_count);
-    }
-    {
-        uwip_kscope ks(ctx, "k_png_finish");
-        k_png_finish<<<F, 256, 0, ctx->stream>>>(cout, g, coff, needed, adler, d_count);
-    }
-    {
-        uwip_kscope ks(ctx, "k_png_assemble");
-        k_png_assemble<<<dim3(g.nch, F), 256, 0, ctx->stream>>>(stage, cout, coff, g, static_cast<const uint8_t *>(d_head), needed, adler,
-                                                                d_streams, slot_bytes, d_sizes, d_count);
-    }
-    UWIP_HIP(ctx, hipGetLastError());
-    return UWIP_OK;
+    uwip_device dev(ctx);
+    encode_sequence(dev, static_cast<const uint8_t *>(frames->data), g, F, filter, static_cast<const uint8_t *>(d_head), d_streams, slot_bytes,
+                    d_sizes, d_count);
+    return dev.finish();
 }
 
 UWIP_API int uwip_png_encode_host(uwip_ctx *ctx, const uwip_batch_u8 *frames, int filter, uint8_t *h_streams, size_t slot_bytes,
                                   int64_t *h_sizes)
 {
     if (!ctx) return uwip_png_encode(ctx, frames, filter, nullptr, 0, nullptr);
-    int rc = uwip_check_batch(ctx, frames, 0);
-    if (rc) return rc;
-    const int F = frames->frames;
-    if (F == 0) return UWIP_OK;
-    UWIP_REQUIRE(ctx, h_sizes != nullptr, "null sizes");
-    UWIP_REQUIRE(ctx, h_streams != nullptr || slot_bytes == 0, "null streams");
-    uint8_t *d_out = static_cast<uint8_t *>(uwip_ws(ctx, "png.streams", (size_t)F * slot_bytes + 16));
-    int64_t *d_sizes = static_cast<int64_t *>(uwip_ws(ctx, "png.sizes", (size_t)F * sizeof(int64_t)));
-    if (!d_out || !d_sizes) return UWIP_ERR_NOMEM;
-    rc = uwip_png_encode(ctx, frames, filter, d_out, slot_bytes, d_sizes);
-    if (rc) return rc;
-    UWIP_HIP(ctx, hipMemcpyAsync(h_sizes, d_sizes, (size_t)F * sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
-    UWIP_HIP(ctx, uwip_stream_wait(ctx));
-    for (int f = 0; f < F; ++f)
-        if (h_sizes[f] > 0)
-            UWIP_HIP(ctx, hipMemcpyAsync(h_streams + (size_t)f * slot_bytes, d_out + (size_t)f * slot_bytes, (size_t)h_sizes[f],
-                                         hipMemcpyDeviceToHost, ctx->stream));
-    UWIP_HIP(ctx, uwip_stream_wait(ctx));
-    return UWIP_OK;
+    return uwip_encode_to_host(ctx, frames, filter, h_streams, slot_bytes, h_sizes, uwip_png_encode, "png.streams", "png.sizes");
 }

@@ -179,6 +179,43 @@ struct uwip_kscope {
     ~uwip_kscope();
 };
 
+// The back end that a codec's host sequence is written against: the sequences (function templates in the first anonymous
+// namespace of jpeg_encode.hip, jpeg_decode.hip, png_encode.hip and png_decode.hip) take no context, only this -- the device
+// here, host threads in tests/hip_on_host.hpp, where the emulation harnesses run the same text under the sanitizers.  The first
+// failure sticks: every later operation does nothing, and the entry point returns finish().
+struct uwip_device {
+    using dim3 = ::dim3;
+    uwip_ctx *ctx;
+    int rc = UWIP_OK;
+    explicit uwip_device(uwip_ctx *c) : ctx(c) {}
+    // `count` elements of T, the named workspace: valid until the context's next call of the same entry point
+    template <class T> T *array(const char *name, size_t count)
+    {
+        if (rc) return nullptr;
+        T *p = static_cast<T *>(uwip_ws(ctx, name, count * sizeof(T)));
+        if (!p) rc = UWIP_ERR_NOMEM;
+        return p;
+    }
+    void fill(void *p, int value, size_t bytes) { if (!rc) hip(hipMemsetAsync(p, value, bytes, ctx->stream), "hipMemsetAsync"); }
+    void copy(void *dst, const void *src, size_t bytes)          // device to device
+    {
+        if (!rc) hip(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, ctx->stream), "hipMemcpyAsync");
+    }
+    // name: what the profile calls this launch (not always the kernel's own name)
+    template <class... P, class... A> void launch(const char *name, void (*kernel)(P...), dim3 grid, unsigned block, A... args)
+    {
+        if (rc) return;
+        uwip_kscope ks(ctx, name);
+        kernel<<<grid, block, 0, ctx->stream>>>(static_cast<P>(args)...);
+    }
+    int finish()
+    {
+        if (!rc) hip(hipGetLastError(), "hipGetLastError()");
+        return rc;
+    }
+    void hip(hipError_t e, const char *what) { if (e != hipSuccess) rc = ctx->fail(UWIP_ERR_HIP, what, hipGetErrorString(e)); }
+};
+
 // First statement of every entry point that allocates, copies or launches: makes the context's device the calling
 // thread's current one (hipSetDevice is thread-local state; a second host thread or a device != 0 would otherwise
 // hipMalloc / launch on whatever device that thread last used).
@@ -228,3 +265,64 @@ static inline bool uwip_aligned_for(const uwip_batch_u8 *b, size_t a)
 }
 
 static inline unsigned uwip_cdiv(size_t a, size_t b) { return (unsigned)((a + b - 1) / b); }
+
+// ---- what the JPEG and the PNG codec's entry points share --------------------------------------------------------------------
+// uwip_jpeg_decode / uwip_png_decode: the checks on (h_streams, h_sizes, n, out, d_status); n == 0 passes, the caller returns
+static inline int uwip_check_streams(uwip_ctx *ctx, const uint8_t *const *h_streams, const size_t *h_sizes, int n, const uwip_batch_u8 *out,
+                                     const int32_t *d_status)
+{
+    UWIP_REQUIRE(ctx, n >= 0 && n <= 65535, "at most 65535 frames per call");
+    UWIP_REQUIRE(ctx, out->frames == n, "the batch must hold one frame per stream");
+    if (n == 0) return UWIP_OK;
+    UWIP_REQUIRE(ctx, h_streams != nullptr && h_sizes != nullptr && d_status != nullptr, "null argument");
+    UWIP_REQUIRE(ctx, out->rows >= 1 && out->cols >= 1, "empty frame");
+    for (int f = 0; f < n; ++f) UWIP_REQUIRE(ctx, h_streams[f] != nullptr || h_sizes[f] == 0, "null stream");
+    for (int f = 0; f < n; ++f) UWIP_REQUIRE(ctx, h_sizes[f] < ((size_t)1 << 28), "a stream of 256 MiB or more");
+    return UWIP_OK;
+}
+
+// uwip_*_decode_host: the device form into the workspace `ws_status`, the statuses down, wait
+template <class Opts>
+static inline int uwip_decode_to_host(uwip_ctx *ctx, const uint8_t *const *h_streams, const size_t *h_sizes, int n, const uwip_batch_u8 *out,
+                                      const Opts *opts, int32_t *h_status,
+                                      int (*decode)(uwip_ctx *, const uint8_t *const *, const size_t *, int, const uwip_batch_u8 *, const Opts *, int32_t *),
+                                      const char *ws_status)
+{
+    if (int rc = uwip_enter(ctx)) return rc;
+    UWIP_REQUIRE(ctx, n >= 0 && (h_status != nullptr || n == 0), "null status");
+    if (n == 0) return UWIP_OK;
+    int32_t *d_status = static_cast<int32_t *>(uwip_ws(ctx, ws_status, (size_t)n * sizeof(int32_t)));
+    if (!d_status) return UWIP_ERR_NOMEM;
+    int rc = decode(ctx, h_streams, h_sizes, n, out, opts, d_status);
+    if (rc) return rc;
+    UWIP_HIP(ctx, hipMemcpyAsync(h_status, d_status, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+    UWIP_HIP(ctx, uwip_stream_wait(ctx));
+    return UWIP_OK;
+}
+
+// uwip_*_encode_host: the device form into the workspaces `ws_streams` / `ws_sizes`, the sizes down, wait, one copy per positive
+// size, wait
+static inline int uwip_encode_to_host(uwip_ctx *ctx, const uwip_batch_u8 *frames, int param, uint8_t *h_streams, size_t slot_bytes,
+                                      int64_t *h_sizes, int (*encode)(uwip_ctx *, const uwip_batch_u8 *, int, uint8_t *, size_t, int64_t *),
+                                      const char *ws_streams, const char *ws_sizes)
+{
+    int rc = uwip_check_batch(ctx, frames, 0);
+    if (rc) return rc;
+    const int F = frames->frames;
+    if (F == 0) return UWIP_OK;
+    UWIP_REQUIRE(ctx, h_sizes != nullptr, "null sizes");
+    UWIP_REQUIRE(ctx, h_streams != nullptr || slot_bytes == 0, "null streams");
+    uint8_t *d_out = static_cast<uint8_t *>(uwip_ws(ctx, ws_streams, (size_t)F * slot_bytes + 16));
+    int64_t *d_sizes = static_cast<int64_t *>(uwip_ws(ctx, ws_sizes, (size_t)F * sizeof(int64_t)));
+    if (!d_out || !d_sizes) return UWIP_ERR_NOMEM;
+    rc = encode(ctx, frames, param, d_out, slot_bytes, d_sizes);
+    if (rc) return rc;
+    UWIP_HIP(ctx, hipMemcpyAsync(h_sizes, d_sizes, (size_t)F * sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
+    UWIP_HIP(ctx, uwip_stream_wait(ctx));
+    for (int f = 0; f < F; ++f)
+        if (h_sizes[f] > 0)
+            UWIP_HIP(ctx, hipMemcpyAsync(h_streams + (size_t)f * slot_bytes, d_out + (size_t)f * slot_bytes, (size_t)h_sizes[f],
+                                         hipMemcpyDeviceToHost, ctx->stream));
+    UWIP_HIP(ctx, uwip_stream_wait(ctx));
+    return UWIP_OK;
+}
