@@ -10,13 +10,16 @@ struct StripOut {
     bool on = false;
     int mode = UWIP_STRIP_FEATHER;
     int max_frames = 1024;
+    bool gain = false;                            // --strip-gain: gain compensation from the overlaps of consecutive key frames
     unsigned detect_flags = 0, match_flags = 0;
     std::shared_ptr<uw::Strip> strip;             // made at the first key frame; declare a StripOut after its context
 
-    // --strip [--strip-mode feather|first|last] [--strip-max N]; false: an unknown mode
+    // --strip [--strip-mode feather|first|last] [--strip-max N] [--strip-gain]; false: an unknown mode.  --strip-gain without
+    // --strip is the caller's to refuse (gain_without_strip)
     bool configure(const Args &a)
     {
         on = a.has("strip");
+        gain = a.has("strip-gain");
         const std::string m = a.get("strip-mode", "feather");
         if (m == "feather") mode = UWIP_STRIP_FEATHER;
         else if (m == "first") mode = UWIP_STRIP_FIRST;
@@ -25,6 +28,7 @@ struct StripOut {
         max_frames = std::max(1, std::atoi(a.get("strip-max", "1024").c_str()));
         return true;
     }
+    bool gain_without_strip() const { return gain && !on; }
     void add(uw::Context &ctx, imgio::Image &im)
     {
         if (!on) return;
@@ -35,10 +39,11 @@ struct StripOut {
     {
         if (!on || !strip) return;
         const std::vector<uwip_strip_segment> segs = strip->layout();
+        if (gain) strip->gains();
         for (size_t i = 0; i < segs.size(); ++i) {
             uw::Mat m;
             imgio::Image im;
-            strip->render((int)i, mode, m, im.data);
+            strip->render((int)i, gain ? mode | UWIP_STRIP_GAIN : mode, m, im.data);
             im.rows = m.rows; im.cols = m.cols; im.channels = 3;
             char name[512];
             std::snprintf(name, sizeof name, "%sstrip_%03zu.%s", prefix.c_str(), i, ext);

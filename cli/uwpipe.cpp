@@ -13,7 +13,8 @@
 // overlap against the current key frame (nan: not compared).
 // --keyframes --strip [--strip-mode feather|first|last]: the enhanced key frames are also chained by their homographies and
 // blended into one image per segment, <prefix>strip_NNN.<ext>, with a "Strip:" line per segment after the table of
-// videostrip_report.txt (cli/stripout.hpp).  Refused with --streams, where the frames never reach the host.
+// videostrip_report.txt (cli/stripout.hpp).  Refused with --streams, where the frames never reach the host.  --strip-gain: with
+// gain compensation from the overlaps of consecutive key frames (uwip_strip_gains); refused without --strip.
 // --device-jpeg: the enhanced frames of a step are encoded on the device (uwip_jpeg_encode_host on the pipe's context, from
 // the step's frames in the staging area) and the files are written from the returned streams: the same bytes as without it.
 // --device-png: the files are .png, encoded on the device in the same way (uwip_png_encode_host): the pixels of --png, other bytes.
@@ -44,7 +45,7 @@ int main(int argc, char **argv)
     if (a.pos.size() < 2 || a.has("h") || a.has("help")) {
         std::printf("uwpipe - bgdehaze -> histretch -> aclahe -> overlap of every frame against its predecessor\n"
                     "usage: uwpipe [-b N] [-c LETTERS] [-w N] [--guard-s] [--min6] [--relative-threshold] [--png] [--device-jpeg]\n"
-                    "              [--device-png] [--device-decode] [--streams] [--keyframes [-k N] [-p X] [--lookback D] [--strip]] <video.avi (Motion-JPEG) | frame_list.txt> <output_prefix>\n"
+                    "              [--device-png] [--device-decode] [--streams] [--keyframes [-k N] [-p X] [--lookback D] [--strip [--strip-gain]]] <video.avi (Motion-JPEG) | frame_list.txt> <output_prefix>\n"
                     "  -b N      frames per step (default 8)\n"
                     "  -c L      histretch letters (default RGB)\n"
                     "  -w N      bgdehaze window (default 15)\n"
@@ -60,7 +61,8 @@ int main(int argc, char **argv)
                     "  --strip       with --keyframes: also blend the enhanced key frames into <prefix>strip_NNN.<ext>, one image per chained\n"
                     "                segment (--strip-mode feather|first|last; --strip-max N key frames, default 1024: the strip keeps them\n"
                     "                at 640 wide in device memory, about 0.7 MB each, allocated at the first one; key frame N + 1 ends the\n"
-                    "                program with an error).  Not with --streams: the frames never reach the host there\n");
+                    "                program with an error).  Not with --streams: the frames never reach the host there\n"
+                    "  --strip-gain  with --strip: one gain per key frame and colour channel from the overlaps of consecutive key frames\n");
         return 0;
     }
     const std::string InputFile = a.pos[0], OutputFile = a.pos[1];
@@ -113,6 +115,7 @@ int main(int argc, char **argv)
         uw::Context strip_ctx(ctx);                        // a view: the context stays this program's
         StripOut strip;
         if (!strip.configure(a)) { std::printf("--strip-mode: feather, first or last\n"); rc = UWIP_ERR_INVALID; what = "--strip-mode"; goto fail; }
+        if (strip.gain_without_strip()) { std::printf("--strip-gain is refused without --strip: there is no strip to compensate\n"); rc = UWIP_ERR_INVALID; what = "--strip-gain"; goto fail; }
         strip.detect_flags = cfg.detect_flags; strip.match_flags = cfg.match_flags;
         if (strip.on && !kf) { std::printf("--strip needs --keyframes: the strip is made of the key frames\n"); rc = UWIP_ERR_INVALID; what = "--strip"; goto fail; }
         if (strip.on && a.has("streams")) {

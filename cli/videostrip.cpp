@@ -9,7 +9,9 @@
 // of the input ends the program with exit code 0 (the reference calls exit(EXIT_FAILURE), B-14).
 // --strip [--strip-mode feather|first|last]: the exported key frames are also chained by their homographies and blended
 // into one image per segment, <prefix>strip_NNN.<ext>, with a "Strip:" line per segment after the report's table
-// (cli/stripout.hpp).  Without the flag the report and the files are what they were.
+// (cli/stripout.hpp).  Without the flag the report and the files are what they were.  --strip-gain: the key frames' levels are
+// compensated first, one gain per key frame and channel from the overlaps of consecutive ones (uwip_strip_gains); refused
+// without --strip.
 #include <cmath>
 #include <fstream>
 #include <thread>
@@ -39,7 +41,7 @@ int main(int argc, char **argv)
     const Args a = parse_args(argc, argv, {"k", "windowSize", "s", "timeSkip", "p", "minOverlap", "g", "gpus", "strip-mode", "strip-max"});
     if (a.pos.size() < 2 || a.has("h") || a.has("help")) {
         std::printf("videostrip - smart extraction of video frames\n"
-                    "usage: videostrip [-k windowSize] [-s timeSkip] [-p minOverlap] [-r] [--png] [--min6] [--relative-threshold] [-g gpus] [--strip [--strip-mode feather|first|last]] <video.avi (Motion-JPEG) | frame_list.txt> <output_prefix>\n"
+                    "usage: videostrip [-k windowSize] [-s timeSkip] [-p minOverlap] [-r] [--png] [--min6] [--relative-threshold] [-g gpus] [--strip [--strip-mode feather|first|last] [--strip-gain]] <video.avi (Motion-JPEG) | frame_list.txt> <output_prefix>\n"
                     "  default: any homography found from >= 4 good matches counts, as in the reference (videostrip.cpp:252-272)\n"
                     "  --min6  a homography needs >= 6 RANSAC inliers, else -2.0 (a deviation; --min4 is accepted and names the default)\n"
                     "  default: fixed detector threshold, as SURF's hessianThreshold is fixed (videostrip.cpp:206)\n"
@@ -48,7 +50,9 @@ int main(int argc, char **argv)
                     "  --strip  also blend the exported key frames into <prefix>strip_NNN.<ext>, one image per chained segment\n"
                     "          (--strip-mode feather|first|last, default feather; --strip-max N key frames, default 1024: the strip keeps\n"
                     "          them at 640 wide in device memory, about 0.7 MB each, allocated at the first one; key frame N + 1 ends the\n"
-                    "          program with an error)\n");
+                    "          program with an error)\n"
+                    "  --strip-gain  with --strip: one gain per key frame and colour channel, solved from the overlaps of consecutive key\n"
+                    "          frames, takes the level steps out of the seams\n");
         return 0;
     }
     const int kWindow = std::atoi(a.get("k", a.get("windowSize", std::to_string(DEFAULT_KWINDOW))).c_str());
@@ -60,6 +64,7 @@ int main(int argc, char **argv)
     const unsigned detect_flags = a.has("relative-threshold") ? UWIP_OVERLAP_RELATIVE_THRESHOLD : 0u;
     StripOut strip_cfg;                                    // the options only: the strip itself lives inside its context's scope
     if (!strip_cfg.configure(a)) { std::printf("--strip-mode: feather, first or last\n"); return EXIT_FAILURE; }
+    if (strip_cfg.gain_without_strip()) { std::printf("--strip-gain is refused without --strip: there is no strip to compensate\n"); return EXIT_FAILURE; }
     strip_cfg.detect_flags = detect_flags; strip_cfg.match_flags = match_flags;
     std::vector<std::string> frames;
     avi::Reader video;

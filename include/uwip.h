@@ -803,7 +803,9 @@ int uwip_pipe_result_params(uwip_pipe *p, uint64_t ticket, int32_t *h_bs, int32_
  * segment by a gather over the canvas: every pixel samples every frame that covers it, bilinearly with 5-bit fractions.
  * The arithmetic is stated once in csrc/strip_core.hpp and is exact: coordinates in float64 without
  * fused operations, everything behind the source position in integers.
- * A quick look, not a mosaic: working resolution only, no exposure compensation, no bundle adjustment, no loop closure.
+ * A quick look, not a mosaic: working resolution only; exposure compensation as one gain per frame and channel from the
+ * overlaps of CONSECUTIVE frames of a segment (uwip_strip_gains, below) -- no pairs that are not consecutive, no bundle
+ * adjustment, no loop closure.
  * A strip is bound to the context it was made from (its stream, its thread rule); destroy it before the context. */
 typedef struct uwip_strip uwip_strip;
 typedef struct uwip_strip_config {
@@ -850,6 +852,35 @@ int uwip_strip_render(uwip_strip *s, int segment, int mode, const uint8_t *fill,
 int uwip_strip_chain_host(int w, int h, int max_canvas_rows, int max_canvas_cols, float max_scale, const double *h_H,
                           const float *h_ratio, int n, double *h_G, double *h_Ginv, int32_t *h_seg, int32_t *h_box,
                           uwip_strip_segment *h_segs, int cap, int *n_segs);
+/* Gain compensation (Brown & Lowe 2007, section 6, restricted to the consecutive pairs of a segment; csrc/strip_core.hpp,
+ * DESIGN.md section 7d).  The key frames are enhanced one by one, so two of the same sea floor differ in level and colour
+ * balance; one gain per frame and channel, solved from the means of the pairs' overlaps, takes the steps out of the seams.
+ *   measure  for every pixel of frame k (not a segment's first) the sample of frame k - 1 at the same plane point; a pixel
+ *            counts when it is covered and all six values (1024 x 8-bit levels) lie in 1024 lo .. 1024 hi; stats[k] = the
+ *            count and the sums of the three samples and of the three pixels, seven uint64 (zeros for a first frame);
+ *   solve    per segment and channel the tridiagonal system of the paper's error with deviations sigma_n (levels) and
+ *            sigma_g (gain), pairs of fewer than min_pixels pixels left out, in float64; gq = the gain in 1/4096,
+ *            clamped to 1024..16384 (0.25..4);
+ *   apply    uwip_strip_render with mode | UWIP_STRIP_GAIN multiplies every sample by its frame's gain, saturating at 255,
+ *            before it is blended; the cover plane is unchanged, and so is every render without the bit. */
+typedef struct uwip_strip_gain_config { float sigma_n, sigma_g; int32_t lo, hi, min_pixels, reserved[3]; } uwip_strip_gain_config;
+#define UWIP_STRIP_GAIN 0x100     /* OR into uwip_strip_render's mode */
+int uwip_strip_gain_config_default(uwip_strip_gain_config *cfg);     /* sigma_n 10, sigma_g 0.1, lo 5, hi 250, min_pixels 64 */
+/* Measure and solve (k_strip_gain_stats, k_strip_gain_solve) for the frames of the last layout.  cfg NULL = the defaults;
+ * sigma_* <= 0, lo > hi, lo or hi outside 0..255 or min_pixels < 1: UWIP_ERR_INVALID.  Without a uwip_strip_layout since the
+ * last add: UWIP_ERR_INVALID, nothing is queued.  Asynchronous.  An add, a reset or a new layout (the first
+ * uwip_strip_layout after an add; listing the same layout again keeps them) drops the gains, and mode | UWIP_STRIP_GAIN
+ * without gains is UWIP_ERR_INVALID. */
+int uwip_strip_gains(uwip_strip *s, const uwip_strip_gain_config *cfg);
+/* Parity tap: h_gq [count][3] i32, h_g [count][3] f64 (the solution before it is quantised), h_stats [count][7] u64; any may be
+ * NULL.  Waits for the stream.  After uwip_strip_set_gains: g = gq / 4096 and the statistics are zero. */
+int uwip_strip_gain_values(uwip_strip *s, int32_t *h_gq, double *h_g, uint64_t *h_stats);
+/* Inject gains instead (host, [count][3], each 1024..16384), after a layout: the parity hook of the gained render. */
+int uwip_strip_set_gains(uwip_strip *s, const int32_t *h_gq);
+/* The solve by itself on the host (the source k_strip_gain_solve runs), no device needed: h_stats [n][7], h_seg [n] as
+ * uwip_strip_transforms returns it, cfg NULL = the defaults -> h_gq [n][3], h_g [n][3] (either may be NULL). */
+int uwip_strip_gain_solve_host(const uint64_t *h_stats, const int32_t *h_seg, int n, const uwip_strip_gain_config *cfg,
+                               int32_t *h_gq, double *h_g);
 
 #ifdef __cplusplus
 }

@@ -274,7 +274,25 @@ public:
         segs_ = segs;
         return segs;
     }
-    // one segment of the last layout(); mode = UWIP_STRIP_FEATHER / FIRST / LAST
+    // after layout(): one gain per frame and channel from the overlaps of consecutive frames (cfg: null = the defaults);
+    // an add or a new layout drops them
+    void gains(const uwip_strip_gain_config *cfg = nullptr) { check(uwip_strip_gains(s_, cfg)); }
+    // the gains in 1/4096 [count][3]; g (the solution before it is quantised) and stats [count][7] when asked for
+    std::vector<int32_t> gain_values(std::vector<double> *g = nullptr, std::vector<uint64_t> *stats = nullptr)
+    {
+        const size_t n = (size_t)count();
+        std::vector<int32_t> gq(3 * n);
+        if (g) g->resize(3 * n);
+        if (stats) stats->resize(7 * n);
+        check(uwip_strip_gain_values(s_, gq.data(), g ? g->data() : nullptr, stats ? stats->data() : nullptr));
+        return gq;
+    }
+    void set_gains(const std::vector<int32_t> &gq)
+    {
+        if (gq.size() != 3 * (size_t)count()) throw Error(UWIP_ERR_INVALID, "Strip::set_gains: [count][3] gains");
+        check(uwip_strip_set_gains(s_, gq.data()));
+    }
+    // one segment of the last layout(); mode = UWIP_STRIP_FEATHER / FIRST / LAST, | UWIP_STRIP_GAIN after gains() / set_gains()
     void render(int segment, int mode, Mat &out, std::vector<uint8_t> &store)
     {
         if (segment < 0 || segment >= (int)segs_.size()) throw Error(UWIP_ERR_INVALID, "Strip::render: no such segment (layout() first)");

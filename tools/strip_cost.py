@@ -2,7 +2,9 @@
 """What the strip mosaic costs on the device: 64 frames of 360 x 640 chained 128 px apart (injected translations), rendered
 after warm-up at least 20 times per mode; k_strip_render is timed by the library's per-kernel device events
 (uwip_prof_enable).  Reported: ms per render, canvas megapixels/s, covered pixel-frames/s, and the ratio to a
-device-to-device copy of the algorithmic bytes (canvas written plus frames read) timed in the same run; `add` per frame
+device-to-device copy of the algorithmic bytes (canvas written plus frames read) timed in the same run; `gains` (the
+statistics of the 63 pairs plus the solve, per-kernel device events and wall clock) and the gained render in each mode
+(k_strip_render_gain) next to the ungained one; `add` per frame
 through detect and match (uw_stream frames, wall clock around a drained stream) and `layout` (wall clock).
 Culling: a render visits the frames of its own segment only, so frames of other segments cost nothing by construction (a
 segment's canvas is the box of all its frames: none of them lies outside it).  What culling costs inside a segment is
@@ -60,6 +62,35 @@ def main():
         ms /= launches
         out["render"][mode] = {"ms": ms, "canvas_mpix_per_s": seg.rows * seg.cols / ms / 1e3, "covered_pixel_frames_per_s": covered / ms * 1e3,
                                "covered_pixel_frames": covered}
+    # gain compensation: `gains` = the memset, k_strip_gain_stats over 63 pairs and k_strip_gain_solve (device events per kernel,
+    # and wall clock around a drained stream for the whole call), then the gained render in each mode
+    for _ in range(3):
+        s.gains()
+    ctx.prof_enable(True)
+    ctx.prof_reset()
+    for _ in range(reps):
+        s.gains()
+    prof = ctx.prof_results()
+    ctx.prof_enable(False)
+    t0 = time.perf_counter()
+    for _ in range(reps):
+        s.gains()
+    wall = (time.perf_counter() - t0) * 1e3 / reps
+    stats_ms, solve_ms = (prof[k][0] / prof[k][1] for k in ("k_strip_gain_stats", "k_strip_gain_solve"))
+    out["gains"] = {"stats_ms": stats_ms, "solve_ms": solve_ms, "ms": stats_ms + solve_ms, "ms_wall": wall, "pairs": n - 1,
+                    "pair_mpix_per_s": (n - 1) * rows * cols / stats_ms / 1e3}
+    out["render_gain"] = {}
+    for mode in ("feather", "first", "last"):
+        for _ in range(3):
+            s.render(0, mode, out=canvas, gain=True)
+        ctx.prof_enable(True)
+        ctx.prof_reset()
+        for _ in range(reps):
+            s.render(0, mode, out=canvas, gain=True)
+        ms, launches = ctx.prof_results()["k_strip_render_gain"]
+        ctx.prof_enable(False)
+        ms /= launches
+        out["render_gain"][mode] = {"ms": ms, "ratio_to_ungained": ms / out["render"][mode]["ms"]}
     # the device-to-device copy of the algorithmic bytes: the canvas written plus every frame read once
     nbytes = seg.rows * seg.cols * 3 + n * rows * cols * 3
     src, dst = torch.empty(nbytes, dtype=torch.uint8, device="cuda"), torch.empty(nbytes, dtype=torch.uint8, device="cuda")

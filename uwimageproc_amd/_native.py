@@ -113,6 +113,13 @@ class StripSegment(C.Structure):
                 ("cols", C.c_int32), ("reserved", C.c_int32 * 2)]
 
 
+class StripGainConfig(C.Structure):
+    """Mirror of ``uwip_strip_gain_config`` (32 bytes)."""
+
+    _fields_ = [("sigma_n", C.c_float), ("sigma_g", C.c_float), ("lo", C.c_int32), ("hi", C.c_int32), ("min_pixels", C.c_int32),
+                ("reserved", C.c_int32 * 3)]
+
+
 # uwip_keyframe_chain_host's callbacks
 KF_OVERLAP_FN = C.CFUNCTYPE(C.c_float, C.c_void_p, C.c_int32, C.c_int32)
 KF_BLUR_FN = C.CFUNCTYPE(C.c_float, C.c_void_p, C.c_int32)
@@ -247,6 +254,11 @@ SIGNATURES = {
     "uwip_strip_render": (C.c_int, [_P, C.c_int, C.c_int, _P, _B, _P]),
     "uwip_strip_chain_host": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, _P, _P, C.c_int, _P, _P, _P, _P,
                                         C.POINTER(StripSegment), C.c_int, C.POINTER(C.c_int)]),
+    "uwip_strip_gain_config_default": (C.c_int, [C.POINTER(StripGainConfig)]),
+    "uwip_strip_gains": (C.c_int, [_P, C.POINTER(StripGainConfig)]),
+    "uwip_strip_gain_values": (C.c_int, [_P, _P, _P, _P]),
+    "uwip_strip_set_gains": (C.c_int, [_P, _P]),
+    "uwip_strip_gain_solve_host": (C.c_int, [_P, _P, C.c_int, C.POINTER(StripGainConfig), _P, _P]),
 }
 
 

@@ -4,7 +4,11 @@
 //   k_strip_render   canvas-centric gather: a workgroup owns a 64 x 16 tile, collects the frames whose box meets it (in
 //                    chunks of kCullChunk, compacted in LDS together with their inverse transforms), every thread keeps
 //                    integer accumulators for its four pixels, the tile is assembled in LDS and written row by row;
-//   k_strip_store    the injected form's copy of frames into the store.
+//   k_strip_store    the injected form's copy of frames into the store;
+//   k_strip_gain_stats  gain compensation, the measurement: a workgroup owns a 64 x 16 tile of frame k, samples frame k - 1 at the
+//                    same plane points, keeps the count and the six sums of the valid pixels in registers, reduces them in
+//                    LDS and adds them to stats[k] with one 64-bit atomic per quantity;
+//   k_strip_gain_solve  one lane runs strip_core.hpp's gain_solve() over the statistics.
 // Everything inside the anonymous namespace is also compiled by the host compiler and run on host threads by
 // tests/strip_emulated.cpp (no HIP-only intrinsics in there).
 #include "uwip_internal.hpp"
@@ -31,6 +35,18 @@ struct StripRender {
     uint8_t *cover;                       // [rows][cols] or null
     uint8_t fill[4];
     int32_t vec;                          // bytes per store of the write-out: 16, 4 or 1
+    const int32_t *gq = nullptr;          // [frames][3] gains in 1/4096 for k_strip_render<MODE, true>; null = none
+};
+
+struct StripGainStats {
+    const uint8_t *store;                 // [frames][h][w][3]
+    size_t fstride;
+    int32_t w, h;
+    const double *G, *Ginv;               // [frames][9]
+    const int32_t *seg;                   // [frames]
+    uwip_sm::GainParams P;
+    unsigned long long *stats;            // [frames][7], cleared before the launch
+    int32_t tiles_x;                      // tiles per row of tiles: blockIdx.x = tile, blockIdx.y = frame
 };
 
 __global__ __launch_bounds__(64) void k_strip_chain(uwip_sm::ChainParams P, const double *H, const float *ratio, int32_t n,
@@ -48,11 +64,59 @@ __global__ __launch_bounds__(256) void k_strip_store(const uint8_t *src, size_t 
     if (x < rowbytes && y < rows) dst[(f * rows + y) * (size_t)rowbytes + x] = src[f * fs + (size_t)y * step + x];
 }
 
-template <int MODE>
+// Frame k = blockIdx.y against frame k - 1.  A thread's four pixels give at most 4 x 255 x 1024, a workgroup's 1024 pixels at
+// most 2^28.0: 32-bit sums up to the workgroup, 64-bit ones beyond it.
+__global__ __launch_bounds__(kRenderThreads) void k_strip_gain_stats(StripGainStats a)
+{
+    __shared__ uint32_t s_sum[uwip_sm::kGainStats][kRenderThreads];
+    const int32_t k = (int32_t)blockIdx.y;
+    if (k == 0 || a.seg[k] != a.seg[k - 1]) return;        // the first frame of a segment has no partner (uniform: no barrier yet)
+    const int32_t tid = (int32_t)threadIdx.x;
+    const int32_t tx0 = ((int32_t)blockIdx.x % a.tiles_x) * kTileW, ty0 = ((int32_t)blockIdx.x / a.tiles_x) * kTileH;
+    const int32_t x = tx0 + (tid & (kTileW - 1)), ly = tid / kTileW;
+    const uint8_t *fk = a.store + (size_t)k * a.fstride, *fp = a.store + (size_t)(k - 1) * a.fstride;
+    double G[9], Ap[9];
+#pragma unroll
+    for (int i = 0; i < 9; ++i) { G[i] = a.G[9 * (size_t)k + i]; Ap[i] = a.Ginv[9 * (size_t)(k - 1) + i]; }
+    uint32_t sum[uwip_sm::kGainStats];
+#pragma unroll
+    for (int q = 0; q < uwip_sm::kGainStats; ++q) sum[q] = 0;
+#pragma unroll
+    for (int j = 0; j < kPix; ++j) {
+        const int32_t y = ty0 + ly + j * (kRenderThreads / kTileW);
+        int32_t Pa[3], Pb[3];
+        if (x >= a.w || y >= a.h || !uwip_sm::gain_pixel(a.P, fk, fp, G, Ap, x, y, a.w, a.h, Pa, Pb)) continue;
+        sum[0] += 1u;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) { sum[1 + c] += (uint32_t)Pa[c]; sum[4 + c] += (uint32_t)Pb[c]; }
+    }
+#pragma unroll
+    for (int q = 0; q < uwip_sm::kGainStats; ++q) s_sum[q][tid] = sum[q];
+    __syncthreads();
+    for (int32_t s = kRenderThreads / 2; s > 0; s >>= 1) {
+        if (tid < s) {
+#pragma unroll
+            for (int q = 0; q < uwip_sm::kGainStats; ++q) s_sum[q][tid] += s_sum[q][tid + s];
+        }
+        __syncthreads();
+    }
+    if (tid < uwip_sm::kGainStats && s_sum[tid][0]) atomicAdd(a.stats + uwip_sm::kGainStats * (size_t)k + tid, (unsigned long long)s_sum[tid][0]);
+}
+
+__global__ __launch_bounds__(64) void k_strip_gain_solve(uwip_sm::GainParams P, const unsigned long long *stats, const int32_t *seg, int32_t n,
+                                                         int32_t *gq, double *g, double *scr)
+{
+    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+    uwip_sm::gain_solve(P, reinterpret_cast<const uint64_t *>(stats), seg, n, gq, g, scr);
+}
+
+// GAIN: every sample is multiplied by its frame's gain (a.gq) before it is blended; false is the kernel without gains
+template <int MODE, bool GAIN = false>
 __global__ __launch_bounds__(kRenderThreads) void k_strip_render(StripRender a)
 {
     __shared__ double s_A[kCullChunk][9];
     __shared__ int32_t s_idx[kCullChunk];
+    __shared__ int32_t s_gq[GAIN ? kCullChunk : 1][3];
     __shared__ uint32_t s_n;
     __shared__ uint32_t s_tile[kTileH * kTileRowBytes / 4];
     const int32_t tid = (int32_t)threadIdx.x;
@@ -79,6 +143,7 @@ __global__ __launch_bounds__(kRenderThreads) void k_strip_render(StripRender a)
                 const uint32_t slot = atomicAdd(&s_n, 1u);
                 s_idx[slot] = g;
                 for (int i = 0; i < 9; ++i) s_A[slot][i] = a.Ginv[9 * (size_t)g + i];
+                if (GAIN) for (int c = 0; c < 3; ++c) s_gq[slot][c] = a.gq[3 * (size_t)g + c];
             }
         }
         __syncthreads();
@@ -90,6 +155,8 @@ __global__ __launch_bounds__(kRenderThreads) void k_strip_render(StripRender a)
             for (int i = 0; i < 9; ++i) A[i] = s_A[e][i];
             const int32_t g = s_idx[e];
             const uint8_t *f = a.store + (size_t)g * a.fstride;
+            int32_t gq[3] = {4096, 4096, 4096};
+            if (GAIN) for (int c = 0; c < 3; ++c) gq[c] = s_gq[e][c];
 #pragma unroll
             for (int j = 0; j < kPix; ++j) {
                 const int32_t Y = ty0 + ly + j * (kRenderThreads / kTileW);
@@ -105,7 +172,8 @@ __global__ __launch_bounds__(kRenderThreads) void k_strip_render(StripRender a)
                 const uint8_t *r0 = f + ((size_t)t.y * a.w) * 3, *r1 = f + ((size_t)t.y1 * a.w) * 3;
 #pragma unroll
                 for (int c = 0; c < 3; ++c) {
-                    const int32_t P = uwip_sm::bilinear(t, r0[t.x * 3 + c], r0[t.x1 * 3 + c], r1[t.x * 3 + c], r1[t.x1 * 3 + c]);
+                    int32_t P = uwip_sm::bilinear(t, r0[t.x * 3 + c], r0[t.x1 * 3 + c], r1[t.x * 3 + c], r1[t.x1 * 3 + c]);
+                    if (GAIN) P = uwip_sm::apply_gain(P, gq[c]);
                     if (MODE == UWIP_STRIP_FEATHER) num[j][c] += (int64_t)t.q * P;
                     else num[j][c] = P;
                 }
@@ -183,6 +251,10 @@ struct uwip_strip {
     std::vector<uwip_strip_segment> h_segs;    // the last layout
     int laid = -1;                         // frame count the last layout saw (-1: none)
     int cursor = 0;                        // next segment uwip_strip_layout returns
+    unsigned long long *stats = nullptr;   // [max_frames][7]: the pairs' statistics (in the block)
+    int32_t *gq = nullptr;                 // [max_frames][3]
+    double *g = nullptr;                   // [max_frames][3]
+    bool gained = false;                   // gains computed or set since the last layout (an add, a reset, a new layout: dropped)
 
     int fail(int code, const char *what) { err = what; return code; }
     int from_ctx(int rc) { if (rc) err = ctx->err; return rc; }
@@ -221,7 +293,8 @@ UWIP_API int uwip_strip_create(uwip_ctx *ctx, const uwip_strip_config *cfg, uwip
     size_t off = 0;
     auto take = [&](size_t bytes) { const size_t at = off; off += align256(bytes); return at; };
     const size_t o_H = take(72 * N), o_G = take(72 * N), o_Gi = take(72 * N), o_fb = take(32 * N), o_ratio = take(4 * N), o_seg = take(4 * N),
-                 o_box = take(16 * N), o_segs = take(sizeof(uwip_strip_segment) * N), o_nseg = take(4);
+                 o_box = take(16 * N), o_segs = take(sizeof(uwip_strip_segment) * N), o_nseg = take(4),
+                 o_stats = take(8 * uwip_sm::kGainStats * N), o_gq = take(12 * N), o_g = take(24 * N);
     void *d = nullptr;
     int rc = uwip_malloc(ctx, off, &d);
     if (!rc) rc = uwip_features_create(ctx, cfg->batch + 1, &s->feats);
@@ -234,6 +307,7 @@ UWIP_API int uwip_strip_create(uwip_ctx *ctx, const uwip_strip_config *cfg, uwip
     s->H = (double *)(s->block + o_H); s->G = (double *)(s->block + o_G); s->Ginv = (double *)(s->block + o_Gi);
     s->fb = (double *)(s->block + o_fb); s->ratio = (float *)(s->block + o_ratio); s->seg = (int32_t *)(s->block + o_seg);
     s->box = (int32_t *)(s->block + o_box); s->segs = (uwip_strip_segment *)(s->block + o_segs); s->nseg = (int32_t *)(s->block + o_nseg);
+    s->stats = (unsigned long long *)(s->block + o_stats); s->gq = (int32_t *)(s->block + o_gq); s->g = (double *)(s->block + o_g);
     s->pq.resize(cfg->batch); s->pt.resize(cfg->batch);
     for (int i = 0; i < cfg->batch; ++i) { s->pq[i] = i + 1; s->pt[i] = i; }
     *out = s;
@@ -254,7 +328,7 @@ UWIP_API int uwip_strip_destroy(uwip_strip *s)
 UWIP_API int uwip_strip_reset(uwip_strip *s)
 {
     if (!s) return UWIP_ERR_INVALID;
-    s->form = 0; s->count = 0; s->last_n = 0; s->have_prev = false; s->laid = -1; s->cursor = 0;
+    s->form = 0; s->count = 0; s->last_n = 0; s->have_prev = false; s->laid = -1; s->cursor = 0; s->gained = false;
     s->h_segs.clear();
     return UWIP_OK;
 }
@@ -332,7 +406,7 @@ UWIP_API int uwip_strip_add(uwip_strip *s, const uwip_batch_u8 *frames, const do
         UWIP_HIP(ctx, hipMemcpyAsync(s->H + 9 * (size_t)s->count, d_H_inject, 72 * (size_t)n, hipMemcpyDeviceToDevice, ctx->stream));
         UWIP_HIP(ctx, hipMemcpyAsync(s->ratio + s->count, d_ratio_inject, 4 * (size_t)n, hipMemcpyDeviceToDevice, ctx->stream));
     }
-    s->form = form; s->have_prev = true; s->last_n = n; s->count += n;
+    s->form = form; s->have_prev = true; s->last_n = n; s->count += n; s->gained = false;
     return UWIP_OK;
 }
 
@@ -349,6 +423,7 @@ static int strip_lay_out(uwip_strip *s)
     uwip_ctx *ctx = s->ctx;
     if (s->laid == s->count) return UWIP_OK;
     s->h_segs.clear();
+    s->gained = false;
     if (s->count > 0) {
         uwip_sm::ChainOut o;
         o.G = s->G; o.Ginv = s->Ginv; o.seg = s->seg; o.box = s->box; o.segs = s->segs; o.nseg = s->nseg;
@@ -406,7 +481,10 @@ UWIP_API int uwip_strip_render(uwip_strip *s, int segment, int mode, const uint8
     if (rc) return s->from_ctx(rc);
     if (s->laid != s->count || s->count == 0) return s->fail(UWIP_ERR_INVALID, "uwip_strip_render: call uwip_strip_layout first");
     if (segment < 0 || segment >= (int)s->h_segs.size()) return s->fail(UWIP_ERR_INVALID, "uwip_strip_render: no such segment");
+    const bool gain = (mode & UWIP_STRIP_GAIN) != 0;
+    mode &= ~UWIP_STRIP_GAIN;
     if (mode != UWIP_STRIP_FEATHER && mode != UWIP_STRIP_FIRST && mode != UWIP_STRIP_LAST) return s->fail(UWIP_ERR_INVALID, "uwip_strip_render: unknown mode");
+    if (gain && !s->gained) return s->fail(UWIP_ERR_INVALID, "uwip_strip_render: UWIP_STRIP_GAIN without uwip_strip_gains or uwip_strip_set_gains since the last layout");
     const uwip_strip_segment &g = s->h_segs[segment];
     if (canvas->frames != 1 || canvas->rows != g.rows || canvas->cols != g.cols)
         return s->fail(UWIP_ERR_INVALID, "uwip_strip_render: the canvas is not one frame of the segment's rows x cols");
@@ -421,11 +499,120 @@ UWIP_API int uwip_strip_render(uwip_strip *s, int segment, int mode, const uint8
     const uintptr_t al = (uintptr_t)canvas->data | (uintptr_t)canvas->step;
     a.vec = al % 16 == 0 ? 16 : (al % 4 == 0 ? 4 : 1);
     const dim3 grid(uwip_cdiv((size_t)g.cols, kTileW), uwip_cdiv((size_t)g.rows, kTileH));
+    if (gain) {
+        a.gq = s->gq;
+        uwip_kscope ks(ctx, "k_strip_render_gain");
+        if (mode == UWIP_STRIP_FEATHER) k_strip_render<UWIP_STRIP_FEATHER, true><<<grid, kRenderThreads, 0, ctx->stream>>>(a);
+        else if (mode == UWIP_STRIP_FIRST) k_strip_render<UWIP_STRIP_FIRST, true><<<grid, kRenderThreads, 0, ctx->stream>>>(a);
+        else k_strip_render<UWIP_STRIP_LAST, true><<<grid, kRenderThreads, 0, ctx->stream>>>(a);
+        UWIP_HIP(ctx, hipGetLastError());
+        return UWIP_OK;
+    }
     uwip_kscope ks(ctx, "k_strip_render");
     if (mode == UWIP_STRIP_FEATHER) k_strip_render<UWIP_STRIP_FEATHER><<<grid, kRenderThreads, 0, ctx->stream>>>(a);
     else if (mode == UWIP_STRIP_FIRST) k_strip_render<UWIP_STRIP_FIRST><<<grid, kRenderThreads, 0, ctx->stream>>>(a);
     else k_strip_render<UWIP_STRIP_LAST><<<grid, kRenderThreads, 0, ctx->stream>>>(a);
     UWIP_HIP(ctx, hipGetLastError());
+    return UWIP_OK;
+}
+
+// ---- gain compensation ----------------------------------------------------------------------------------------------------
+UWIP_API int uwip_strip_gain_config_default(uwip_strip_gain_config *cfg)
+{
+    if (!cfg) return UWIP_ERR_INVALID;
+    std::memset(cfg, 0, sizeof *cfg);
+    cfg->sigma_n = 10.0f; cfg->sigma_g = 0.1f;
+    cfg->lo = 5; cfg->hi = 250; cfg->min_pixels = 64;
+    return UWIP_OK;
+}
+
+static bool gain_config_ok(const uwip_strip_gain_config &c)
+{
+    return c.sigma_n > 0.0f && c.sigma_g > 0.0f && c.sigma_n <= 3.0e38f && c.sigma_g <= 3.0e38f && c.lo >= 0 && c.hi <= 255 && c.lo <= c.hi &&
+           c.min_pixels >= 1;
+}
+
+static uwip_sm::GainParams gain_params(const uwip_strip_gain_config *cfg)
+{
+    uwip_strip_gain_config c;
+    if (cfg) c = *cfg; else uwip_strip_gain_config_default(&c);
+    uwip_sm::GainParams P;
+    P.sigma_n = (double)c.sigma_n; P.sigma_g = (double)c.sigma_g; P.lo = c.lo; P.hi = c.hi; P.min_pixels = c.min_pixels;
+    return P;
+}
+
+UWIP_API int uwip_strip_gains(uwip_strip *s, const uwip_strip_gain_config *cfg)
+{
+    if (!s) return UWIP_ERR_INVALID;
+    uwip_ctx *ctx = s->ctx;
+    if (int rc_e = uwip_enter(ctx)) return s->from_ctx(rc_e);
+    if (cfg && !gain_config_ok(*cfg)) return s->fail(UWIP_ERR_INVALID, "uwip_strip_gains: sigma_n, sigma_g > 0, 0 <= lo <= hi <= 255, min_pixels >= 1");
+    if (s->laid != s->count || s->count == 0) return s->fail(UWIP_ERR_INVALID, "uwip_strip_gains: call uwip_strip_layout first");
+    const uwip_sm::GainParams P = gain_params(cfg);
+    const size_t N = (size_t)s->count;
+    if (hipError_t e = hipMemsetAsync(s->stats, 0, 8 * uwip_sm::kGainStats * N, ctx->stream)) return s->from_ctx(ctx->fail(UWIP_ERR_HIP, "hipMemsetAsync", hipGetErrorString(e)));
+    StripGainStats a;
+    a.store = s->store; a.fstride = (size_t)s->w * s->h * 3; a.w = s->w; a.h = s->h;
+    a.G = s->G; a.Ginv = s->Ginv; a.seg = s->seg; a.P = P; a.stats = s->stats;
+    a.tiles_x = (int32_t)uwip_cdiv((size_t)s->w, kTileW);
+    {
+        uwip_kscope ks(ctx, "k_strip_gain_stats");
+        k_strip_gain_stats<<<dim3((unsigned)a.tiles_x * uwip_cdiv((size_t)s->h, kTileH), (unsigned)s->count), kRenderThreads, 0, ctx->stream>>>(a);
+        if (hipError_t e = hipGetLastError()) return s->from_ctx(ctx->fail(UWIP_ERR_HIP, "k_strip_gain_stats", hipGetErrorString(e)));
+    }
+    {
+        uwip_kscope ks(ctx, "k_strip_gain_solve");
+        k_strip_gain_solve<<<1, 64, 0, ctx->stream>>>(P, s->stats, s->seg, s->count, s->gq, s->g, s->fb);     // fb: free once the chain has run
+        if (hipError_t e = hipGetLastError()) return s->from_ctx(ctx->fail(UWIP_ERR_HIP, "k_strip_gain_solve", hipGetErrorString(e)));
+    }
+    s->gained = true;
+    return UWIP_OK;
+}
+
+UWIP_API int uwip_strip_gain_values(uwip_strip *s, int32_t *h_gq, double *h_g, uint64_t *h_stats)
+{
+    if (!s) return UWIP_ERR_INVALID;
+    if (int rc_e = uwip_enter(s->ctx)) return s->from_ctx(rc_e);
+    if (s->laid != s->count || !s->gained) return s->fail(UWIP_ERR_INVALID, "uwip_strip_gain_values: no gains since the last layout");
+    const size_t N = (size_t)s->count;
+    int rc = UWIP_OK;
+    if (!rc && h_gq) rc = uwip_memcpy_d2h(s->ctx, h_gq, s->gq, 12 * N);
+    if (!rc && h_g) rc = uwip_memcpy_d2h(s->ctx, h_g, s->g, 24 * N);
+    if (!rc && h_stats) rc = uwip_memcpy_d2h(s->ctx, h_stats, s->stats, 8 * uwip_sm::kGainStats * N);
+    return s->from_ctx(rc);
+}
+
+UWIP_API int uwip_strip_set_gains(uwip_strip *s, const int32_t *h_gq)
+{
+    if (!s) return UWIP_ERR_INVALID;
+    if (int rc_e = uwip_enter(s->ctx)) return s->from_ctx(rc_e);
+    if (!h_gq) return s->fail(UWIP_ERR_INVALID, "uwip_strip_set_gains: h_gq");
+    if (s->laid != s->count || s->count == 0) return s->fail(UWIP_ERR_INVALID, "uwip_strip_set_gains: call uwip_strip_layout first");
+    const size_t N = (size_t)s->count;
+    std::vector<double> g(3 * N);
+    for (size_t i = 0; i < 3 * N; ++i) {
+        if (h_gq[i] < 1024 || h_gq[i] > 16384) return s->fail(UWIP_ERR_INVALID, "uwip_strip_set_gains: a gain outside 1024..16384");
+        g[i] = (double)h_gq[i] / 4096.0;
+    }
+    // the taps of injected gains: g = gq / 4096, no statistics
+    int rc = uwip_memcpy_h2d(s->ctx, s->gq, h_gq, 12 * N);
+    if (!rc) rc = uwip_memcpy_h2d(s->ctx, s->g, g.data(), 24 * N);
+    if (rc) return s->from_ctx(rc);
+    if (hipError_t e = hipMemsetAsync(s->stats, 0, 8 * uwip_sm::kGainStats * N, s->ctx->stream)) return s->from_ctx(s->ctx->fail(UWIP_ERR_HIP, "hipMemsetAsync", hipGetErrorString(e)));
+    s->gained = true;
+    return UWIP_OK;
+}
+
+UWIP_API int uwip_strip_gain_solve_host(const uint64_t *h_stats, const int32_t *h_seg, int n, const uwip_strip_gain_config *cfg, int32_t *h_gq,
+                                        double *h_g)
+{
+    if (n < 0 || (n > 0 && (!h_stats || !h_seg)) || (cfg && !gain_config_ok(*cfg))) return UWIP_ERR_INVALID;
+    const size_t N = (size_t)n;
+    std::vector<double> g(3 * N), scr(3 * N);
+    std::vector<int32_t> gq(3 * N);
+    uwip_sm::gain_solve(gain_params(cfg), h_stats, h_seg, n, gq.data(), g.data(), scr.data());
+    if (h_gq) std::copy(gq.begin(), gq.end(), h_gq);
+    if (h_g) std::copy(g.begin(), g.end(), h_g);
     return UWIP_OK;
 }
 

@@ -1,6 +1,7 @@
-// The arithmetic of the strip mosaic, stated ONCE for the device (strip.hip: k_strip_chain, k_strip_render), the host
-// (uwip_strip_chain_host) and the emulation harness (tests/strip_emulated.cpp).  tests/_strip_mirror.py restates it in numpy
-// and takes nothing from here; the tests compare the two bit for bit, which is why
+// The arithmetic of the strip mosaic, stated ONCE for the device (strip.hip: k_strip_chain, k_strip_render, k_strip_gain_stats,
+// k_strip_gain_solve), the host (uwip_strip_chain_host, uwip_strip_gain_solve_host) and the emulation harnesses
+// (tests/strip_emulated.cpp, tests/strip_gain_emulated.cpp).  tests/_strip_mirror.py and tests/_strip_gain_mirror.py restate it
+// in numpy and take nothing from here; the tests compare the two bit for bit, which is why
 //   - every coordinate is float64, products and sums are separate operations (the library and the harness are built with
 //     -ffp-contract=off), sums are written ((a*x) + (b*y)) + c, and divisions are IEEE divisions;
 //   - everything after the source position (u, v) is integer arithmetic.
@@ -186,6 +187,101 @@ STRIP_HD inline bool sample(const double *A, double px, double py, int32_t w, in
 STRIP_HD inline int32_t bilinear(const Tap &t, int32_t p00, int32_t p10, int32_t p01, int32_t p11)
 {
     return (32 - t.fx) * (32 - t.fy) * p00 + t.fx * (32 - t.fy) * p10 + (32 - t.fx) * t.fy * p01 + t.fx * t.fy * p11;
+}
+
+// ---- gain compensation from the overlaps of consecutive frames (Brown & Lowe 2007, section 6) ----------------------------
+// One gain per frame and colour channel, from the pairs (k - 1, k) inside a segment alone: the normal equations are
+// tridiagonal.  k_strip_gain_stats measures the pairs, gain_solve() solves, apply_gain() is the render's multiply.
+struct GainParams {
+    double  sigma_n, sigma_g;             // the paper's error and gain deviations, in 8-bit levels / as a factor
+    int32_t lo, hi;                       // a pixel counts when all six of its values lie in 1024 lo .. 1024 hi
+    int32_t min_pixels;                   // a pair with fewer valid pixels counts as having none
+};
+constexpr int kGainStats = 7;             // N, Sa[3], Sb[3] per frame: its pair with the frame before
+
+// pixel (x, y) of a frame under its G -> the point on the segment's plane; false = no such point
+STRIP_HD inline bool gain_point(const double *G, double x, double y, double &px, double &py)
+{
+    const double d = ((G[6] * x) + (G[7] * y)) + G[8];
+    if (!(d > 0.0)) return false;
+    px = (((G[0] * x) + (G[1] * y)) + G[2]) / d;
+    py = (((G[3] * x) + (G[4] * y)) + G[5]) / d;
+    return finite_d(px) && finite_d(py);
+}
+
+// One pixel of frame k against frame k - 1: fk / fp are the two frames (w x h BGR, packed), G of frame k, Ap = Ginv of frame
+// k - 1.  Pb = 1024 x the pixel, Pa = the bilinear sample of frame k - 1 at the same plane point; false = not a valid pixel.
+STRIP_HD inline bool gain_pixel(const GainParams &P, const uint8_t *fk, const uint8_t *fp, const double *G, const double *Ap,
+                                int32_t x, int32_t y, int32_t w, int32_t h, int32_t *Pa, int32_t *Pb)
+{
+    double px, py;
+    Tap t;
+    if (!gain_point(G, (double)x, (double)y, px, py)) return false;
+    if (!sample(Ap, px, py, w, h, t)) return false;
+    const uint8_t *b = fk + ((size_t)y * w + x) * 3;
+    const uint8_t *r0 = fp + ((size_t)t.y * w) * 3, *r1 = fp + ((size_t)t.y1 * w) * 3;
+    const int32_t lo = 1024 * P.lo, hi = 1024 * P.hi;
+    bool ok = true;
+    for (int c = 0; c < 3; ++c) {
+        Pb[c] = 1024 * (int32_t)b[c];
+        Pa[c] = bilinear(t, r0[t.x * 3 + c], r0[t.x1 * 3 + c], r1[t.x * 3 + c], r1[t.x1 * 3 + c]);
+        ok = ok && Pa[c] >= lo && Pa[c] <= hi && Pb[c] >= lo && Pb[c] <= hi;
+    }
+    return ok;
+}
+
+STRIP_HD inline int32_t gain_quantise(double g)
+{
+    const double v = floor((g * 4096.0) + 0.5);
+    if (!finite_d(v)) return 4096;
+    return v < 1024.0 ? 1024 : (v > 16384.0 ? 16384 : (int32_t)v);
+}
+
+// The solve: stats [n][7] (a segment's first frame: zeros), seg [n] -> gq [n][3] (gains in 1/4096, 1024 .. 16384), g [n][3].
+// `scr` is scratch of [n][3] doubles (diag, off, rhs of one segment and channel; the elimination overwrites diag and rhs).
+STRIP_HD inline void gain_solve(const GainParams &P, const uint64_t *stats, const int32_t *seg, int32_t n, int32_t *gq, double *g,
+                                double *scr)
+{
+    const double wN = 1.0 / (P.sigma_n * P.sigma_n), wg = 1.0 / (P.sigma_g * P.sigma_g);
+    for (int32_t first = 0; first < n;) {
+        int32_t end = first + 1;
+        while (end < n && seg[end] == seg[first]) ++end;
+        const int32_t m = end - first;
+        double *diag = scr, *off = scr + m, *rhs = scr + 2 * (size_t)m;
+        for (int c = 0; c < 3; ++c) {
+            for (int32_t i = 0; i < m; ++i) { diag[i] = 0.0; off[i] = 0.0; rhs[i] = 0.0; }
+            for (int32_t i = 1; i < m; ++i) {                        // the pair (a, b) = (i - 1, i)
+                const uint64_t *st = stats + kGainStats * (size_t)(first + i);
+                if (st[0] < (uint64_t)P.min_pixels) continue;        // counts as N = 0: the pair adds nothing
+                const double Nd = (double)st[0];
+                const double A = (double)st[1 + c] / (Nd * 1024.0), B = (double)st[4 + c] / (Nd * 1024.0);
+                diag[i - 1] = diag[i - 1] + (Nd * (((A * A) * wN) + wg));
+                diag[i] = diag[i] + (Nd * (((B * B) * wN) + wg));
+                off[i - 1] = -(Nd * ((A * B) * wN));
+                rhs[i - 1] = rhs[i - 1] + (Nd * wg);
+                rhs[i] = rhs[i] + (Nd * wg);
+            }
+            for (int32_t i = 0; i < m; ++i) if (diag[i] == 0.0) { diag[i] = 1.0; rhs[i] = 1.0; }
+            // Thomas elimination: forwards (diag becomes c, rhs becomes e), then backwards
+            for (int32_t i = 1; i < m; ++i) {
+                const double mul = off[i - 1] / diag[i - 1];
+                diag[i] = diag[i] - (mul * off[i - 1]);
+                rhs[i] = rhs[i] - (mul * rhs[i - 1]);
+            }
+            double *go = g + 3 * (size_t)first + c;
+            go[3 * (size_t)(m - 1)] = rhs[m - 1] / diag[m - 1];
+            for (int32_t i = m - 2; i >= 0; --i) go[3 * (size_t)i] = (rhs[i] - (off[i] * go[3 * (size_t)(i + 1)])) / diag[i];
+            for (int32_t i = 0; i < m; ++i) gq[3 * (size_t)(first + i) + c] = gain_quantise(go[3 * (size_t)i]);
+        }
+        first = end;
+    }
+}
+
+// P (0 .. 255 * 1024) times a gain in 1/4096, saturating: 261120 x 16384 + 2048 < 2^32
+STRIP_HD inline int32_t apply_gain(int32_t P, int32_t gq)
+{
+    const uint32_t v = ((uint32_t)P * (uint32_t)gq + 2048u) >> 12;
+    return (int32_t)(v < 255u * 1024u ? v : 255u * 1024u);
 }
 
 }  // namespace uwip_sm

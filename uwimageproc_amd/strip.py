@@ -8,9 +8,10 @@ from typing import List, NamedTuple, Optional
 
 import numpy as np
 
-from ._native import UWIP_OK, Context, StripConfig, StripSegment, UwipError, batch_of
+from ._native import UWIP_OK, Context, StripConfig, StripGainConfig, StripSegment, UwipError, batch_of
 
 MODES = {"feather": 0, "first": 1, "last": 2}          # UWIP_STRIP_FEATHER / FIRST / LAST
+GAIN = 0x100                                           # UWIP_STRIP_GAIN
 
 
 class Segment(NamedTuple):
@@ -107,9 +108,39 @@ class Strip:
         self._check(self._l.uwip_strip_transforms(self._h, G.ctypes.data, Gi.ctypes.data, seg.ctypes.data, box.ctypes.data))
         return {"G": G, "Ginv": Gi, "seg": seg, "box": box}
 
-    def render(self, segment: int, mode: str = "feather", fill=(0, 0, 0), cover: bool = False, out: "Optional[torch.Tensor]" = None):
+    def gains(self, **cfg):
+        """After ``layout``: measure the overlaps of consecutive frames and solve one gain per frame and channel
+        (uwip_strip_gains).  Keywords are fields of uwip_strip_gain_config (sigma_n, sigma_g, lo, hi, min_pixels) over its
+        defaults.  An ``add``, a ``reset`` or a new layout drops the gains."""
+        c = StripGainConfig()
+        self._check(self._l.uwip_strip_gain_config_default(C.byref(c)))
+        for k, v in cfg.items():
+            if k not in ("sigma_n", "sigma_g", "lo", "hi", "min_pixels"):
+                raise TypeError(f"unknown uwip_strip_gain_config field {k!r}")
+            setattr(c, k, v)
+        self._check(self._l.uwip_strip_gains(self._h, C.byref(c)))
+        self.ctx.sync()
+
+    def gain_values(self):
+        """After ``gains`` or ``set_gains``: dict of gq [n, 3] int32 (gains in 1/4096), g [n, 3] float64, stats [n, 7] uint64
+        (N, Sa[3], Sb[3] of each frame's pair with the frame before it) (numpy)."""
+        n = len(self)
+        gq, g, st = np.zeros((n, 3), np.int32), np.zeros((n, 3)), np.zeros((n, 7), np.uint64)
+        self._check(self._l.uwip_strip_gain_values(self._h, gq.ctypes.data, g.ctypes.data, st.ctypes.data))
+        return {"gq": gq, "g": g, "stats": st}
+
+    def set_gains(self, gq):
+        """After ``layout``: inject gains [n, 3] in 1/4096, each 1024..16384, instead of computing them."""
+        gq = np.ascontiguousarray(gq, np.int32)
+        if gq.shape != (len(self), 3):
+            raise ValueError("gq: [frames, 3]")
+        self._check(self._l.uwip_strip_set_gains(self._h, gq.ctypes.data))
+
+    def render(self, segment: int, mode: str = "feather", fill=(0, 0, 0), cover: bool = False, out: "Optional[torch.Tensor]" = None,
+               gain: bool = False):
         """One segment of the last ``layout``: a uint8 tensor [rows, cols, 3] (``out``: a tensor of that shape to render
-        into, any row stride), and with ``cover`` also the [rows, cols] count of covering frames."""
+        into, any row stride), and with ``cover`` also the [rows, cols] count of covering frames.  ``gain``: every sample
+        times its frame's gain (``gains`` or ``set_gains`` first)."""
         import torch
 
         if not self.segments:
@@ -127,6 +158,6 @@ class Strip:
         b = batch_of(out)
         f = (C.c_uint8 * 3)(*[int(v) for v in fill])
         torch.cuda.current_stream(dev).synchronize()
-        self._check(self._l.uwip_strip_render(self._h, int(segment), MODES[mode], f, C.byref(b), C.c_void_p(cov.data_ptr()) if cover else None))
+        self._check(self._l.uwip_strip_render(self._h, int(segment), MODES[mode] | (GAIN if gain else 0), f, C.byref(b), C.c_void_p(cov.data_ptr()) if cover else None))
         self.ctx.sync()
         return (out, cov) if cover else out
