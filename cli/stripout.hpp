@@ -11,11 +11,12 @@ struct StripOut {
     int mode = UWIP_STRIP_FEATHER;
     int max_frames = 1024;
     bool gain = false;                            // --strip-gain: gain compensation from the overlaps of consecutive key frames
+    int levels = 4;                               // --strip-levels: levels of the stacks of --strip-mode multiband (ramps 1, 2, 4, 8)
     unsigned detect_flags = 0, match_flags = 0;
     std::shared_ptr<uw::Strip> strip;             // made at the first key frame; declare a StripOut after its context
 
-    // --strip [--strip-mode feather|first|last] [--strip-max N] [--strip-gain]; false: an unknown mode.  --strip-gain without
-    // --strip is the caller's to refuse (gain_without_strip)
+    // --strip [--strip-mode feather|first|last|multiband] [--strip-levels N] [--strip-max N] [--strip-gain]; false: an unknown
+    // mode or levels outside 1..4.  --strip-gain without --strip is the caller's to refuse (gain_without_strip)
     bool configure(const Args &a)
     {
         on = a.has("strip");
@@ -24,7 +25,10 @@ struct StripOut {
         if (m == "feather") mode = UWIP_STRIP_FEATHER;
         else if (m == "first") mode = UWIP_STRIP_FIRST;
         else if (m == "last") mode = UWIP_STRIP_LAST;
+        else if (m == "multiband") mode = UWIP_STRIP_MULTIBAND;
         else return false;
+        levels = std::atoi(a.get("strip-levels", "4").c_str());
+        if (levels < 1 || levels > 4) return false;
         max_frames = std::max(1, std::atoi(a.get("strip-max", "1024").c_str()));
         return true;
     }
@@ -40,6 +44,12 @@ struct StripOut {
         if (!on || !strip) return;
         const std::vector<uwip_strip_segment> segs = strip->layout();
         if (gain) strip->gains();
+        if (mode == UWIP_STRIP_MULTIBAND) {               // after the last add: the stacks of every key frame
+            uwip_strip_bands_config bc;
+            uwip_strip_bands_config_default(&bc);
+            bc.levels = levels;
+            strip->bands(&bc);
+        }
         for (size_t i = 0; i < segs.size(); ++i) {
             uw::Mat m;
             imgio::Image im;

@@ -804,8 +804,8 @@ int uwip_pipe_result_params(uwip_pipe *p, uint64_t ticket, int32_t *h_bs, int32_
  * The arithmetic is stated once in csrc/strip_core.hpp and is exact: coordinates in float64 without
  * fused operations, everything behind the source position in integers.
  * A quick look, not a mosaic: working resolution only; exposure compensation as one gain per frame and channel from the
- * overlaps of CONSECUTIVE frames of a segment (uwip_strip_gains, below) -- no pairs that are not consecutive, no bundle
- * adjustment, no loop closure.
+ * overlaps of CONSECUTIVE frames of a segment (uwip_strip_gains, below) and multi-band blending along the feather weights
+ * (uwip_strip_bands, below) -- no pairs that are not consecutive, no seam finding, no bundle adjustment, no loop closure.
  * A strip is bound to the context it was made from (its stream, its thread rule); destroy it before the context. */
 typedef struct uwip_strip uwip_strip;
 typedef struct uwip_strip_config {
@@ -881,6 +881,33 @@ int uwip_strip_set_gains(uwip_strip *s, const int32_t *h_gq);
  * uwip_strip_transforms returns it, cfg NULL = the defaults -> h_gq [n][3], h_g [n][3] (either may be NULL). */
 int uwip_strip_gain_solve_host(const uint64_t *h_stats, const int32_t *h_seg, int n, const uwip_strip_gain_config *cfg,
                                int32_t *h_gq, double *h_g);
+/* Multi-band blending (Brown & Lowe 2007, section 7; csrc/strip_core.hpp): low frequencies are blended
+ * over a wide zone and high frequencies over a narrow one, so levels join smoothly while texture stays sharp where two
+ * misregistered frames meet.  No pyramid of the canvas: every frame carries an undecimated stack in its own coordinates.
+ *   stack    level 0 is the stored frame; level l + 1 = level l under (1, 4, 6, 4, 1) x (1, 4, 6, 4, 1) with taps 2^l pixels
+ *            apart, borders clamped: (sum + 128) >> 8, one rounding per level, u8;
+ *   render   a covering frame k has one tap and one feather weight q_k (those of the other modes); S[k][l] = the bilinear
+ *            sample of its level l (times the frame's gain with UWIP_STRIP_GAIN), D[k][l] = S[k][l] - S[k][l+1]; the band
+ *            weight w[k][l] = max(0, q_k - max_k q_k + ramp[l]) is a ramp of ramp[l] feather units behind the best frame
+ *            (1: winner takes all, ties share); b = sum_l round(sum_k w D / sum_k w), the last level is blended with the
+ *            weights q_k themselves, out = clamp(floor((sum q S[levels] + (b + 512) sum q) / (1024 sum q)), 0, 255).
+ * A pixel that one frame covers is what UWIP_STRIP_FIRST gives; the cover plane is that of the other modes. */
+typedef struct uwip_strip_bands_config { int32_t levels; int32_t ramp[4]; int32_t reserved[3]; } uwip_strip_bands_config;
+#define UWIP_STRIP_MULTIBAND 3    /* uwip_strip_render's mode, alone or with UWIP_STRIP_GAIN; uwip_strip_bands first */
+int uwip_strip_bands_config_default(uwip_strip_bands_config *cfg);   /* levels 4, ramps 1, 2, 4, 8 */
+/* Build the stacks of every frame added so far (k_strip_stack, one launch per level) and keep the ramps for the renders.
+ * cfg NULL = the defaults; levels outside 1..4, a ramp[l] for l < levels outside 1..4096, or no frame: UWIP_ERR_INVALID, nothing
+ * is queued.  The stacks' store (levels x count x rows x cols x 3 bytes of the stored geometry) is allocated here, not at
+ * uwip_strip_create, and freed by uwip_strip_reset and uwip_strip_destroy; a failed allocation returns UWIP_ERR_NOMEM and
+ * leaves the strip as it was, without stacks.  Asynchronous.  An add or a reset drops the stacks (UWIP_STRIP_MULTIBAND without
+ * them is UWIP_ERR_INVALID); a new layout keeps them: they depend on the frames alone. */
+int uwip_strip_bands(uwip_strip *s, const uwip_strip_bands_config *cfg);
+/* Parity tap: level 1..levels of a frame's stack, h_out [rows][cols][3] u8 of the stored geometry, packed.  Waits for the
+ * stream. */
+int uwip_strip_band_level(uwip_strip *s, int frame, int level, uint8_t *h_out);
+/* The stack by itself on the host (the source k_strip_stack runs), no device needed: frame [h][w][3] u8 packed, levels 1..4
+ * -> out [levels][h][w][3].  A null pointer, w or h outside 1..32768 or levels outside 1..4: UWIP_ERR_INVALID. */
+int uwip_strip_stack_host(const uint8_t *frame, int w, int h, int levels, uint8_t *out);
 
 #ifdef __cplusplus
 }

@@ -292,7 +292,12 @@ public:
         if (gq.size() != 3 * (size_t)count()) throw Error(UWIP_ERR_INVALID, "Strip::set_gains: [count][3] gains");
         check(uwip_strip_set_gains(s_, gq.data()));
     }
-    // one segment of the last layout(); mode = UWIP_STRIP_FEATHER / FIRST / LAST, | UWIP_STRIP_GAIN after gains() / set_gains()
+    // the stacks of every frame added so far, for UWIP_STRIP_MULTIBAND (cfg: null = 4 levels, ramps 1, 2, 4, 8); an add drops them
+    void bands(const uwip_strip_bands_config *cfg = nullptr) { check(uwip_strip_bands(s_, cfg)); }
+    // level 1..levels of a frame's stack: rows x cols x 3 bytes of the stored geometry (the caller sizes `out`)
+    void band_level(int frame, int level, uint8_t *out) { check(uwip_strip_band_level(s_, frame, level, out)); }
+    // one segment of the last layout(); mode = UWIP_STRIP_FEATHER / FIRST / LAST, or MULTIBAND after bands(),
+    // | UWIP_STRIP_GAIN after gains() / set_gains()
     void render(int segment, int mode, Mat &out, std::vector<uint8_t> &store)
     {
         if (segment < 0 || segment >= (int)segs_.size()) throw Error(UWIP_ERR_INVALID, "Strip::render: no such segment (layout() first)");

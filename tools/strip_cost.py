@@ -4,7 +4,9 @@ after warm-up at least 20 times per mode; k_strip_render is timed by the library
 (uwip_prof_enable).  Reported: ms per render, canvas megapixels/s, covered pixel-frames/s, and the ratio to a
 device-to-device copy of the algorithmic bytes (canvas written plus frames read) timed in the same run; `gains` (the
 statistics of the 63 pairs plus the solve, per-kernel device events and wall clock) and the gained render in each mode
-(k_strip_render_gain) next to the ungained one; `add` per frame
+(k_strip_render_gain) next to the ungained one; `bands` (k_strip_stack per level and in all) and the multiband render,
+ungained and gained (k_strip_render_bands, k_strip_render_bands_gain), next to FEATHER of the same run, on both workloads;
+`add` per frame
 through detect and match (uw_stream frames, wall clock around a drained stream) and `layout` (wall clock).
 Culling: a render visits the frames of its own segment only, so frames of other segments cost nothing by construction (a
 segment's canvas is the box of all its frames: none of them lies outside it).  What culling costs inside a segment is
@@ -23,6 +25,35 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import uwimageproc_amd as uw  # noqa: E402
 from uwimageproc_amd import synth  # noqa: E402
+
+
+def timed(ctx, key, reps, call):
+    """ms per launch of the kernel(s) `key` (one name or several: their sum) over `reps` calls after three warm-up calls"""
+    for _ in range(3):
+        call()
+    ctx.prof_enable(True)
+    ctx.prof_reset()
+    for _ in range(reps):
+        call()
+    prof = ctx.prof_results()
+    ctx.prof_enable(False)
+    keys = [key] if isinstance(key, str) else key
+    return [prof[k][0] / reps for k in keys]
+
+
+def multiband(ctx, s, canvas, reps, feather_ms, copy_ms, gained):
+    """bands with the defaults and the multiband renders of segment 0, next to this run's FEATHER and device-to-device copy"""
+    stack = timed(ctx, ["k_strip_stack_1", "k_strip_stack_2", "k_strip_stack_4", "k_strip_stack_8"], reps, s.bands)
+    out = {"levels": 4, "ramp": [1, 2, 4, 8], "stack_ms_per_level": stack, "stack_ms": sum(stack)}
+    ms = timed(ctx, "k_strip_render_bands", reps, lambda: s.render(0, "multiband", out=canvas))[0]
+    out["render"] = {"ms": ms, "ratio_to_feather": ms / feather_ms}
+    if gained:
+        msg = timed(ctx, "k_strip_render_bands_gain", reps, lambda: s.render(0, "multiband", out=canvas, gain=True))[0]
+        out["render_gain"] = {"ms": msg, "ratio_to_ungained": msg / ms, "ratio_to_feather": msg / feather_ms}
+    if copy_ms:
+        out["stack_ratio_to_d2d_copy"] = sum(stack) / copy_ms
+        out["render"]["ratio_to_d2d_copy"] = ms / copy_ms
+    return out
 
 
 def main():
@@ -106,6 +137,8 @@ def main():
     out["d2d_copy"] = {"bytes": nbytes, "ms": copy_ms, "gb_per_s": 2 * nbytes / copy_ms / 1e6}
     for mode in out["render"]:
         out["render"][mode]["ratio_to_d2d_copy"] = out["render"][mode]["ms"] / copy_ms
+    # multi-band blending on the same strip: the stacks of the 64 frames, then the render next to this run's FEATHER
+    out["multiband"] = multiband(ctx, s, canvas, reps, out["render"]["feather"]["ms"], copy_ms, gained=True)
     s.close()
     del frames, canvas, src, dst
     # culling inside a segment: 1024 frames 15 px apart
@@ -133,6 +166,10 @@ def main():
     out["cull_in_segment_1024_frames"] = {"canvas": [seg2.rows, seg2.cols], "pitch_px": pitch2, "ms": ms2, "covered_pixel_frames": covered2,
                                           "ns_per_covered_pixel_frame": ms2 * 1e6 / covered2,
                                           "ns_per_covered_pixel_frame_64_frames": f64["ms"] * 1e6 / f64["covered_pixel_frames"]}
+    s.gains()
+    mb2 = multiband(ctx, s, canvas2, reps, ms2, 0.0, gained=True)
+    mb2["feather_ms"] = ms2
+    out["multiband_1024_frames"] = mb2
     s.close()
     del f2, canvas2, cover2
     # add through resize, detect and match: 16 frames per call, the stream drained around the timed calls

@@ -120,6 +120,12 @@ class StripGainConfig(C.Structure):
                 ("reserved", C.c_int32 * 3)]
 
 
+class StripBandsConfig(C.Structure):
+    """Mirror of ``uwip_strip_bands_config`` (32 bytes)."""
+
+    _fields_ = [("levels", C.c_int32), ("ramp", C.c_int32 * 4), ("reserved", C.c_int32 * 3)]
+
+
 # uwip_keyframe_chain_host's callbacks
 KF_OVERLAP_FN = C.CFUNCTYPE(C.c_float, C.c_void_p, C.c_int32, C.c_int32)
 KF_BLUR_FN = C.CFUNCTYPE(C.c_float, C.c_void_p, C.c_int32)
@@ -259,6 +265,10 @@ SIGNATURES = {
     "uwip_strip_gain_values": (C.c_int, [_P, _P, _P, _P]),
     "uwip_strip_set_gains": (C.c_int, [_P, _P]),
     "uwip_strip_gain_solve_host": (C.c_int, [_P, _P, C.c_int, C.POINTER(StripGainConfig), _P, _P]),
+    "uwip_strip_bands_config_default": (C.c_int, [C.POINTER(StripBandsConfig)]),
+    "uwip_strip_bands": (C.c_int, [_P, C.POINTER(StripBandsConfig)]),
+    "uwip_strip_band_level": (C.c_int, [_P, C.c_int, C.c_int, _P]),
+    "uwip_strip_stack_host": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P]),
 }
 
 

@@ -8,7 +8,9 @@
 //   k_strip_gain_stats  gain compensation, the measurement: a workgroup owns a 64 x 16 tile of frame k, samples frame k - 1 at the
 //                    same plane points, keeps the count and the six sums of the valid pixels in registers, reduces them in
 //                    LDS and adds them to stats[k] with one 64-bit atomic per quantity;
-//   k_strip_gain_solve  one lane runs strip_core.hpp's gain_solve() over the statistics.
+//   k_strip_gain_solve  one lane runs strip_core.hpp's gain_solve() over the statistics;
+//   k_strip_stack    multi-band blending, the frames' stacks: one level of every frame per launch, the tile and its halo in LDS;
+//   k_strip_render_bands  the gather of k_strip_render, one pixel per thread, blending the stacks' bands (UWIP_STRIP_MULTIBAND).
 // Everything inside the anonymous namespace is also compiled by the host compiler and run on host threads by
 // tests/strip_emulated.cpp (no HIP-only intrinsics in there).
 #include "uwip_internal.hpp"
@@ -229,6 +231,224 @@ __global__ __launch_bounds__(kRenderThreads) void k_strip_render(StripRender a)
         }
     }
 }
+
+// ---- multi-band blending ------------------------------------------------------------------------------------------------------
+struct StripStack {
+    const uint8_t *in;                    // [frames][h][w][3]: level l
+    uint8_t *out;                         // [frames][h][w][3]: level l + 1
+    size_t fstride;
+    int32_t w, h, s;                      // s = 2^l: the distance of the taps
+    int32_t tiles_x;                      // tiles per row of tiles: blockIdx.x = tile, blockIdx.y = frame
+    int32_t vec;                          // 4: both bases, the frame stride and 3 w are multiples of 4 (whole words); 1: bytes
+};
+
+struct StripBands {
+    StripRender r;                        // as k_strip_render takes it
+    const uint8_t *bands;                 // [levels][bcount][h][w][3]: levels 1 .. levels of every frame
+    size_t lstride;                       // bcount x fstride
+    uwip_sm::BandParams P;
+};
+
+constexpr int kStackRows = kTileH + 4 * 8;                          // the tile and a halo of 2 s rows, at s = 8
+constexpr int kStackRowWords = (kTileRowBytes + 12 * 8) / 4;       // and of 6 s bytes on either side (s = 1: 2 more, to a word)
+constexpr int kBandTileH = kRenderThreads / kTileW;                 // the multiband render's tile: 64 x 4, one pixel per thread
+
+// Level l + 1 of every frame from level l.  A frame's rows are bytes here: the taps of a byte lie 3 s bytes apart, and beyond a
+// row's ends each byte takes its own channel of the first / last pixel.  The tile's rows with their halo go into LDS from a
+// start that is a multiple of 4 bytes, as whole words wherever a word lies inside the row.
+__global__ __launch_bounds__(kRenderThreads) void k_strip_stack(StripStack a)
+{
+    __shared__ uint32_t s_in[kStackRows * kStackRowWords];
+    const int32_t tid = (int32_t)threadIdx.x;
+    const int32_t tx0 = ((int32_t)blockIdx.x % a.tiles_x) * kTileW, ty0 = ((int32_t)blockIdx.x / a.tiles_x) * kTileH;
+    const uint8_t *in = a.in + (size_t)blockIdx.y * a.fstride;
+    uint8_t *out = a.out + (size_t)blockIdx.y * a.fstride;
+    const int32_t s = a.s, pad = (6 * s) & 3, rb = 3 * a.w;
+    const int32_t Ba = tx0 * 3 - 6 * s - pad;                                      // the row byte of LDS byte 0: a multiple of 4
+    const int32_t rw = (kTileRowBytes + 12 * s + pad + 3) / 4, rows = kTileH + 4 * s;
+    for (int32_t i = tid; i < rows * rw; i += kRenderThreads) {
+        const int32_t r = i / rw, j = i % rw, B = Ba + 4 * j;
+        const uint8_t *row = in + (size_t)uwip_sm::clampi(ty0 - 2 * s + r, 0, a.h - 1) * rb;
+        uint32_t v = 0;
+        if (a.vec == 4 && B >= 0 && B + 4 <= rb) {
+            v = *reinterpret_cast<const uint32_t *>(row + B);
+        } else {
+#pragma unroll
+            for (int q = 0; q < 4; ++q) v |= (uint32_t)row[uwip_sm::stack_clamp_byte(B + q, a.w)] << (8 * q);
+        }
+        s_in[r * kStackRowWords + j] = v;
+    }
+    __syncthreads();
+    const uint8_t *lds = reinterpret_cast<const uint8_t *>(s_in);
+    const int32_t th = min(kTileH, a.h - ty0), nb = min(kTileRowBytes, rb - tx0 * 3);   // rows of this tile, bytes of each
+    constexpr int U = kTileRowBytes / 4;
+    for (int32_t i = tid; i < kTileH * U; i += kRenderThreads) {
+        const int32_t r = i / U, at = (i % U) * 4;
+        if (r >= th || at >= nb) continue;
+        uint32_t v = 0;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            int32_t sum = 0;
+#pragma unroll
+            for (int ii = 0; ii < 5; ++ii) {
+                const uint8_t *p = lds + (r + ii * s) * (kStackRowWords * 4) + pad + at + q;
+                int32_t rs = 0;
+#pragma unroll
+                for (int jj = 0; jj < 5; ++jj) rs += uwip_sm::stack_k(jj) * (int32_t)p[3 * s * jj];
+                sum += uwip_sm::stack_k(ii) * rs;
+            }
+            v |= (uint32_t)uwip_sm::stack_round(sum) << (8 * q);
+        }
+        uint8_t *p = out + (size_t)(ty0 + r) * rb + (size_t)tx0 * 3 + at;
+        if (a.vec == 4 && at + 4 <= nb) {
+            *reinterpret_cast<uint32_t *>(p) = v;
+        } else {
+            for (int32_t q = 0; q < 4 && at + q < nb; ++q) p[q] = (uint8_t)(v >> (8 * q));
+        }
+    }
+}
+
+// UWIP_STRIP_MULTIBAND: the gather of k_strip_render with one pixel per thread on a 64 x 4 tile and two passes over the listed
+// frames -- the first finds the pixel's largest feather weight (and its cover count), the second samples every level a frame
+// has a weight in and accumulates the bands' sums and the residual's.  A frame whose band weights are all zero costs the
+// residual level's taps alone.
+template <bool GAIN>
+__global__ __launch_bounds__(kRenderThreads) void k_strip_render_bands(StripBands b)
+{
+    __shared__ double s_A[kCullChunk][9];
+    __shared__ int32_t s_idx[kCullChunk];
+    __shared__ int32_t s_gq[GAIN ? kCullChunk : 1][3];
+    __shared__ uint32_t s_n;
+    __shared__ uint32_t s_tile[kBandTileH * kTileRowBytes / 4];
+    constexpr int L = uwip_sm::kBandLevels;
+    const StripRender &a = b.r;
+    const int32_t tid = (int32_t)threadIdx.x;
+    const int32_t tx0 = (int32_t)blockIdx.x * kTileW, ty0 = (int32_t)blockIdx.y * kBandTileH;
+    const int32_t tx1 = min(tx0 + kTileW, a.cols) - 1, ty1 = min(ty0 + kBandTileH, a.rows) - 1;
+    const int32_t lx = tid & (kTileW - 1), ly = tid / kTileW;
+    const int32_t X = tx0 + lx, Y = ty0 + ly;
+    const bool inside = X <= tx1 && Y <= ty1;
+    const double px = (double)(X + a.x0), py = (double)(Y + a.y0);
+    const int32_t levels = b.P.levels;
+
+    int64_t N[L][3], W[L], NL[3] = {0, 0, 0}, WL = 0;
+#pragma unroll
+    for (int l = 0; l < L; ++l) { N[l][0] = N[l][1] = N[l][2] = 0; W[l] = 0; }
+    int32_t qmax = 0;
+    uint32_t cnt = 0;
+
+    for (int pass = 0; pass < 2; ++pass) {
+        for (int32_t base = 0; base < a.count; base += kCullChunk) {
+            __syncthreads();                               // the previous chunk's list has been read by everyone
+            if (tid == 0) s_n = 0;
+            __syncthreads();
+            for (int32_t k = base + tid; k < min(base + kCullChunk, a.count); k += kRenderThreads) {
+                const int32_t g = a.first + k;
+                const int32_t *bx = a.box + 4 * (size_t)g;
+                if (bx[0] <= tx1 && bx[2] >= tx0 && bx[1] <= ty1 && bx[3] >= ty0) {
+                    const uint32_t slot = atomicAdd(&s_n, 1u);
+                    s_idx[slot] = g;
+                    for (int i = 0; i < 9; ++i) s_A[slot][i] = a.Ginv[9 * (size_t)g + i];
+                    if (GAIN) for (int c = 0; c < 3; ++c) s_gq[slot][c] = a.gq[3 * (size_t)g + c];
+                }
+            }
+            __syncthreads();
+            const int32_t n = (int32_t)s_n;
+            if (!inside) continue;                         // a pixel beyond the canvas: nothing to accumulate (barriers stay uniform)
+            for (int32_t e = 0; e < n; ++e) {
+                double A[9];
+#pragma unroll
+                for (int i = 0; i < 9; ++i) A[i] = s_A[e][i];
+                uwip_sm::Tap t;
+                if (!uwip_sm::sample(A, px, py, a.w, a.h, t)) continue;
+                if (pass == 0) {
+                    qmax = t.q > qmax ? t.q : qmax;
+                    cnt += 1u;
+                    continue;
+                }
+                const int32_t g = s_idx[e];
+                int32_t gq[3] = {4096, 4096, 4096};
+                if (GAIN) for (int c = 0; c < 3; ++c) gq[c] = s_gq[e][c];
+                int32_t wl[L];
+#pragma unroll
+                for (int l = 0; l < L; ++l) wl[l] = l < levels ? uwip_sm::band_weight(t.q, qmax, b.P.ramp[l]) : 0;
+                const size_t o0 = ((size_t)t.y * a.w) * 3, o1 = ((size_t)t.y1 * a.w) * 3;
+                int32_t prev[3] = {0, 0, 0};               // S[l - 1], when level l - 1 has a weight
+#pragma unroll
+                for (int l = 0; l <= L; ++l) {
+                    if (l > levels) continue;
+                    const bool last = l == levels;
+                    const bool need = last || wl[l < L ? l : L - 1] > 0 || (l > 0 && wl[l - 1] > 0);
+                    if (!need) continue;
+                    const uint8_t *f = l == 0 ? a.store + (size_t)g * a.fstride : b.bands + (size_t)(l - 1) * b.lstride + (size_t)g * a.fstride;
+                    const uint8_t *r0 = f + o0, *r1 = f + o1;
+                    int32_t S[3];
+#pragma unroll
+                    for (int c = 0; c < 3; ++c) {
+                        S[c] = uwip_sm::bilinear(t, r0[t.x * 3 + c], r0[t.x1 * 3 + c], r1[t.x * 3 + c], r1[t.x1 * 3 + c]);
+                        if (GAIN) S[c] = uwip_sm::apply_gain(S[c], gq[c]);
+                    }
+                    if (l > 0 && wl[l - 1] > 0) {
+#pragma unroll
+                        for (int c = 0; c < 3; ++c) N[l - 1][c] += (int64_t)wl[l - 1] * (int64_t)(prev[c] - S[c]);
+                        W[l - 1] += wl[l - 1];
+                    }
+                    if (last) {
+#pragma unroll
+                        for (int c = 0; c < 3; ++c) NL[c] += (int64_t)t.q * S[c];
+                        WL += t.q;
+                    }
+#pragma unroll
+                    for (int c = 0; c < 3; ++c) prev[c] = S[c];
+                }
+            }
+        }
+    }
+
+    uint8_t *tile = reinterpret_cast<uint8_t *>(s_tile);
+    if (inside) {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            uint8_t v = a.fill[c];
+            if (cnt > 0u) {
+                int64_t bsum = 0;
+#pragma unroll
+                for (int l = 0; l < L; ++l) if (l < levels) bsum += uwip_sm::band_term(N[l][c], W[l]);
+                v = uwip_sm::band_pixel(NL[c], WL, bsum);
+            }
+            tile[ly * kTileRowBytes + lx * 3 + c] = v;
+        }
+        if (a.cover) a.cover[(size_t)Y * a.cols + X] = (uint8_t)(cnt > 255u ? 255u : cnt);
+    }
+    __syncthreads();
+    const int32_t th = ty1 - ty0 + 1, nb = (tx1 - tx0 + 1) * 3;       // rows of this tile, bytes of each
+    uint8_t *out = a.canvas + (size_t)ty0 * a.step + (size_t)tx0 * 3;
+    if (a.vec == 16) {
+        constexpr int U = kTileRowBytes / 16;
+        for (int32_t i = tid; i < kBandTileH * U; i += kRenderThreads) {
+            const int32_t r = i / U, at = (i % U) * 16;
+            if (r >= th || at >= nb) continue;
+            uint8_t *p = out + (size_t)r * a.step + at;
+            const uint32_t *s = s_tile + (r * kTileRowBytes + at) / 4;
+            if (at + 16 <= nb) *reinterpret_cast<uint4 *>(p) = make_uint4(s[0], s[1], s[2], s[3]);
+            else for (int32_t q = at; q < nb; ++q) out[(size_t)r * a.step + q] = tile[r * kTileRowBytes + q];
+        }
+    } else if (a.vec == 4) {
+        constexpr int U = kTileRowBytes / 4;
+        for (int32_t i = tid; i < kBandTileH * U; i += kRenderThreads) {
+            const int32_t r = i / U, at = (i % U) * 4;
+            if (r >= th || at >= nb) continue;
+            uint8_t *p = out + (size_t)r * a.step + at;
+            if (at + 4 <= nb) *reinterpret_cast<uint32_t *>(p) = s_tile[(r * kTileRowBytes + at) / 4];
+            else for (int32_t q = at; q < nb; ++q) out[(size_t)r * a.step + q] = tile[r * kTileRowBytes + q];
+        }
+    } else {
+        for (int32_t i = tid; i < kBandTileH * kTileRowBytes; i += kRenderThreads) {
+            const int32_t r = i / kTileRowBytes, at = i % kTileRowBytes;
+            if (r < th && at < nb) out[(size_t)r * a.step + at] = tile[i];
+        }
+    }
+}
 }  // namespace
 
 struct uwip_strip {
@@ -255,6 +475,10 @@ struct uwip_strip {
     int32_t *gq = nullptr;                 // [max_frames][3]
     double *g = nullptr;                   // [max_frames][3]
     bool gained = false;                   // gains computed or set since the last layout (an add, a reset, a new layout: dropped)
+    uint8_t *bands = nullptr;              // [levels][band_count][h][w][3]: the frames' stacks, allocated by uwip_strip_bands
+    size_t bands_bytes = 0;
+    int band_count = 0;                    // frames the stacks were built for
+    uwip_sm::BandParams band{};            // levels 0: no stacks (an add, a reset: dropped; a new layout keeps them)
 
     int fail(int code, const char *what) { err = what; return code; }
     int from_ctx(int rc) { if (rc) err = ctx->err; return rc; }
@@ -320,6 +544,7 @@ UWIP_API int uwip_strip_destroy(uwip_strip *s)
     if (uwip_enter(s->ctx) == UWIP_OK) (void)uwip_stream_wait(s->ctx);
     if (s->feats) uwip_features_destroy(s->feats);
     if (s->store) uwip_free(s->ctx, s->store);
+    if (s->bands) uwip_free(s->ctx, s->bands);
     if (s->block) uwip_free(s->ctx, s->block);
     delete s;
     return UWIP_OK;
@@ -330,6 +555,12 @@ UWIP_API int uwip_strip_reset(uwip_strip *s)
     if (!s) return UWIP_ERR_INVALID;
     s->form = 0; s->count = 0; s->last_n = 0; s->have_prev = false; s->laid = -1; s->cursor = 0; s->gained = false;
     s->h_segs.clear();
+    s->band.levels = 0;
+    if (s->bands) {                                        // the stacks' store goes with the frames: a strip that asks again pays again
+        if (uwip_enter(s->ctx) == UWIP_OK) (void)uwip_stream_wait(s->ctx);
+        uwip_free(s->ctx, s->bands);
+        s->bands = nullptr; s->bands_bytes = 0;
+    }
     return UWIP_OK;
 }
 
@@ -406,7 +637,7 @@ UWIP_API int uwip_strip_add(uwip_strip *s, const uwip_batch_u8 *frames, const do
         UWIP_HIP(ctx, hipMemcpyAsync(s->H + 9 * (size_t)s->count, d_H_inject, 72 * (size_t)n, hipMemcpyDeviceToDevice, ctx->stream));
         UWIP_HIP(ctx, hipMemcpyAsync(s->ratio + s->count, d_ratio_inject, 4 * (size_t)n, hipMemcpyDeviceToDevice, ctx->stream));
     }
-    s->form = form; s->have_prev = true; s->last_n = n; s->count += n; s->gained = false;
+    s->form = form; s->have_prev = true; s->last_n = n; s->count += n; s->gained = false; s->band.levels = 0;
     return UWIP_OK;
 }
 
@@ -483,7 +714,10 @@ UWIP_API int uwip_strip_render(uwip_strip *s, int segment, int mode, const uint8
     if (segment < 0 || segment >= (int)s->h_segs.size()) return s->fail(UWIP_ERR_INVALID, "uwip_strip_render: no such segment");
     const bool gain = (mode & UWIP_STRIP_GAIN) != 0;
     mode &= ~UWIP_STRIP_GAIN;
-    if (mode != UWIP_STRIP_FEATHER && mode != UWIP_STRIP_FIRST && mode != UWIP_STRIP_LAST) return s->fail(UWIP_ERR_INVALID, "uwip_strip_render: unknown mode");
+    if (mode != UWIP_STRIP_FEATHER && mode != UWIP_STRIP_FIRST && mode != UWIP_STRIP_LAST && mode != UWIP_STRIP_MULTIBAND)
+        return s->fail(UWIP_ERR_INVALID, "uwip_strip_render: unknown mode");
+    if (mode == UWIP_STRIP_MULTIBAND && (s->band.levels == 0 || s->band_count != s->count))
+        return s->fail(UWIP_ERR_INVALID, "uwip_strip_render: UWIP_STRIP_MULTIBAND without uwip_strip_bands since the last add");
     if (gain && !s->gained) return s->fail(UWIP_ERR_INVALID, "uwip_strip_render: UWIP_STRIP_GAIN without uwip_strip_gains or uwip_strip_set_gains since the last layout");
     const uwip_strip_segment &g = s->h_segs[segment];
     if (canvas->frames != 1 || canvas->rows != g.rows || canvas->cols != g.cols)
@@ -498,6 +732,22 @@ UWIP_API int uwip_strip_render(uwip_strip *s, int segment, int mode, const uint8
     // the tile's rows start at multiples of 192 bytes from the row's start: base and step decide the store width
     const uintptr_t al = (uintptr_t)canvas->data | (uintptr_t)canvas->step;
     a.vec = al % 16 == 0 ? 16 : (al % 4 == 0 ? 4 : 1);
+    if (mode == UWIP_STRIP_MULTIBAND) {
+        StripBands b;
+        b.r = a; b.bands = s->bands; b.lstride = (size_t)s->band_count * a.fstride; b.P = s->band;
+        const dim3 bgrid(uwip_cdiv((size_t)g.cols, kTileW), uwip_cdiv((size_t)g.rows, kBandTileH));
+        if (gain) {
+            b.r.gq = s->gq;
+            uwip_kscope ks(ctx, "k_strip_render_bands_gain");
+            k_strip_render_bands<true><<<bgrid, kRenderThreads, 0, ctx->stream>>>(b);
+            UWIP_HIP(ctx, hipGetLastError());
+            return UWIP_OK;
+        }
+        uwip_kscope ks(ctx, "k_strip_render_bands");
+        k_strip_render_bands<false><<<bgrid, kRenderThreads, 0, ctx->stream>>>(b);
+        UWIP_HIP(ctx, hipGetLastError());
+        return UWIP_OK;
+    }
     const dim3 grid(uwip_cdiv((size_t)g.cols, kTileW), uwip_cdiv((size_t)g.rows, kTileH));
     if (gain) {
         a.gq = s->gq;
@@ -513,6 +763,87 @@ UWIP_API int uwip_strip_render(uwip_strip *s, int segment, int mode, const uint8
     else if (mode == UWIP_STRIP_FIRST) k_strip_render<UWIP_STRIP_FIRST><<<grid, kRenderThreads, 0, ctx->stream>>>(a);
     else k_strip_render<UWIP_STRIP_LAST><<<grid, kRenderThreads, 0, ctx->stream>>>(a);
     UWIP_HIP(ctx, hipGetLastError());
+    return UWIP_OK;
+}
+
+// ---- multi-band blending ------------------------------------------------------------------------------------------------------
+UWIP_API int uwip_strip_bands_config_default(uwip_strip_bands_config *cfg)
+{
+    if (!cfg) return UWIP_ERR_INVALID;
+    std::memset(cfg, 0, sizeof *cfg);
+    cfg->levels = 4;
+    for (int l = 0; l < 4; ++l) cfg->ramp[l] = 1 << l;
+    return UWIP_OK;
+}
+
+static bool bands_config_ok(const uwip_strip_bands_config &c)
+{
+    if (c.levels < 1 || c.levels > uwip_sm::kBandLevels) return false;
+    for (int l = 0; l < c.levels; ++l) if (c.ramp[l] < 1 || c.ramp[l] > 4096) return false;
+    return true;
+}
+
+UWIP_API int uwip_strip_bands(uwip_strip *s, const uwip_strip_bands_config *cfg)
+{
+    if (!s) return UWIP_ERR_INVALID;
+    uwip_ctx *ctx = s->ctx;
+    if (int rc_e = uwip_enter(ctx)) return s->from_ctx(rc_e);
+    uwip_strip_bands_config c;
+    if (cfg) c = *cfg; else uwip_strip_bands_config_default(&c);
+    if (!bands_config_ok(c)) return s->fail(UWIP_ERR_INVALID, "uwip_strip_bands: levels 1..4, ramp[l] 1..4096 for l < levels");
+    if (s->count == 0) return s->fail(UWIP_ERR_INVALID, "uwip_strip_bands: no frame");
+    const size_t fstride = (size_t)s->w * s->h * 3, lstride = fstride * (size_t)s->count, need = lstride * (size_t)c.levels;
+    if (need > s->bands_bytes) {
+        if (s->bands) {
+            if (hipError_t e = uwip_stream_wait(ctx)) return s->from_ctx(ctx->fail(UWIP_ERR_HIP, "uwip_stream_wait", hipGetErrorString(e)));
+            uwip_free(ctx, s->bands);
+            s->bands = nullptr; s->bands_bytes = 0; s->band.levels = 0;
+        }
+        void *d = nullptr;
+        if (int rc = uwip_malloc(ctx, need, &d)) return s->from_ctx(rc);
+        s->bands = (uint8_t *)d; s->bands_bytes = need;
+    }
+    StripStack a;
+    a.fstride = fstride; a.w = s->w; a.h = s->h;
+    a.tiles_x = (int32_t)uwip_cdiv((size_t)s->w, kTileW);
+    a.vec = (s->w * 3) % 4 == 0 ? 4 : 1;                    // the stores' bases are allocations: rows of whole words decide
+    const dim3 grid((unsigned)a.tiles_x * uwip_cdiv((size_t)s->h, kTileH), (unsigned)s->count);
+    for (int l = 0; l < c.levels; ++l) {
+        a.in = l == 0 ? s->store : s->bands + (size_t)(l - 1) * lstride;
+        a.out = s->bands + (size_t)l * lstride;
+        a.s = 1 << l;
+        static const char *const names[uwip_sm::kBandLevels] = {"k_strip_stack_1", "k_strip_stack_2", "k_strip_stack_4", "k_strip_stack_8"};
+        uwip_kscope ks(ctx, names[l]);                      // the profile keeps the levels apart, by their tap distance
+        k_strip_stack<<<grid, kRenderThreads, 0, ctx->stream>>>(a);
+        if (hipError_t e = hipGetLastError()) { s->band.levels = 0; return s->from_ctx(ctx->fail(UWIP_ERR_HIP, "k_strip_stack", hipGetErrorString(e))); }
+    }
+    s->band.levels = c.levels;
+    for (int l = 0; l < uwip_sm::kBandLevels; ++l) s->band.ramp[l] = l < c.levels ? c.ramp[l] : 1;
+    s->band_count = s->count;
+    return UWIP_OK;
+}
+
+UWIP_API int uwip_strip_band_level(uwip_strip *s, int frame, int level, uint8_t *h_out)
+{
+    if (!s) return UWIP_ERR_INVALID;
+    if (int rc_e = uwip_enter(s->ctx)) return s->from_ctx(rc_e);
+    if (!h_out) return s->fail(UWIP_ERR_INVALID, "uwip_strip_band_level: h_out");
+    if (s->band.levels == 0 || s->band_count != s->count) return s->fail(UWIP_ERR_INVALID, "uwip_strip_band_level: no stacks since the last add");
+    if (frame < 0 || frame >= s->count || level < 1 || level > s->band.levels) return s->fail(UWIP_ERR_INVALID, "uwip_strip_band_level: no such frame or level");
+    const size_t fstride = (size_t)s->w * s->h * 3;
+    return s->from_ctx(uwip_memcpy_d2h(s->ctx, h_out, s->bands + ((size_t)(level - 1) * s->band_count + frame) * fstride, fstride));
+}
+
+UWIP_API int uwip_strip_stack_host(const uint8_t *frame, int w, int h, int levels, uint8_t *out)
+{
+    if (!frame || !out || w < 1 || h < 1 || w > 32768 || h > 32768 || levels < 1 || levels > uwip_sm::kBandLevels) return UWIP_ERR_INVALID;
+    const size_t fstride = (size_t)w * h * 3;
+    for (int l = 0; l < levels; ++l) {
+        const uint8_t *in = l == 0 ? frame : out + (size_t)(l - 1) * fstride;
+        uint8_t *o = out + (size_t)l * fstride;
+        for (int y = 0; y < h; ++y)
+            for (int B = 0; B < 3 * w; ++B) o[(size_t)y * w * 3 + B] = uwip_sm::stack_byte(in, w, h, 1 << l, y, B);
+    }
     return UWIP_OK;
 }
 

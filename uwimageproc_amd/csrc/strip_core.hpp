@@ -1,6 +1,7 @@
 // The arithmetic of the strip mosaic, stated ONCE for the device (strip.hip: k_strip_chain, k_strip_render, k_strip_gain_stats,
-// k_strip_gain_solve), the host (uwip_strip_chain_host, uwip_strip_gain_solve_host) and the emulation harnesses
-// (tests/strip_emulated.cpp, tests/strip_gain_emulated.cpp).  tests/_strip_mirror.py and tests/_strip_gain_mirror.py restate it
+// k_strip_gain_solve, k_strip_stack, k_strip_render_bands), the host (uwip_strip_chain_host, uwip_strip_gain_solve_host,
+// uwip_strip_stack_host) and the emulation harnesses (tests/strip_emulated.cpp, tests/strip_gain_emulated.cpp,
+// tests/strip_band_emulated.cpp).  tests/_strip_mirror.py, tests/_strip_gain_mirror.py and tests/_strip_band_mirror.py restate it
 // in numpy and take nothing from here; the tests compare the two bit for bit, which is why
 //   - every coordinate is float64, products and sums are separate operations (the library and the harness are built with
 //     -ffp-contract=off), sums are written ((a*x) + (b*y)) + c, and divisions are IEEE divisions;
@@ -282,6 +283,67 @@ STRIP_HD inline int32_t apply_gain(int32_t P, int32_t gq)
 {
     const uint32_t v = ((uint32_t)P * (uint32_t)gq + 2048u) >> 12;
     return (int32_t)(v < 255u * 1024u ? v : 255u * 1024u);
+}
+
+// ---- multi-band blending (Brown & Lowe 2007, section 7) ------------------------------------------------------------------
+// Every frame carries an undecimated (a trous) stack in its own coordinates: level 0 is the frame, level l + 1 is level l under
+// (1, 4, 6, 4, 1) x (1, 4, 6, 4, 1) / 256 with taps 2^l pixels apart, borders clamped, one rounding per level.  The render
+// samples every level at the frame's one tap, blends the differences of consecutive levels with a ramp of ramp[l] feather units
+// behind the best frame, and the last level with the feather weights themselves.
+constexpr int kBandLevels = 4;            // most levels of a stack
+
+struct BandParams {
+    int32_t levels;                       // 1 .. kBandLevels
+    int32_t ramp[kBandLevels];            // 1 .. 4096 each
+};
+
+STRIP_HD inline int32_t stack_k(int i) { return i == 2 ? 6 : ((i == 1 || i == 3) ? 4 : 1); }
+
+// A frame's rows as bytes: byte B of a row of 3 w bytes, B anywhere -> the byte the clamp reads (its own channel of the row's
+// first or last pixel)
+STRIP_HD inline int32_t stack_clamp_byte(int32_t B, int32_t w)
+{
+    if (B < 0) return ((B % 3) + 3) % 3;
+    if (B >= 3 * w) return 3 * (w - 1) + B % 3;
+    return B;
+}
+
+STRIP_HD inline uint8_t stack_round(int32_t sum) { return (uint8_t)((sum + 128) >> 8); }
+
+// byte B of row y of the next level, from the level `in` (w x h BGR, packed) with taps s pixels apart
+STRIP_HD inline uint8_t stack_byte(const uint8_t *in, int32_t w, int32_t h, int32_t s, int32_t y, int32_t B)
+{
+    int32_t sum = 0;
+    for (int i = 0; i < 5; ++i) {
+        const uint8_t *row = in + (size_t)clampi(y + (i - 2) * s, 0, h - 1) * w * 3;
+        int32_t r = 0;
+        for (int j = 0; j < 5; ++j) r += stack_k(j) * (int32_t)row[stack_clamp_byte(B + 3 * s * (j - 2), w)];
+        sum += stack_k(i) * r;
+    }
+    return stack_round(sum);
+}
+
+// a / b towards minus infinity, b > 0
+STRIP_HD inline int64_t floor_div(int64_t a, int64_t b)
+{
+    const int64_t q = a / b;
+    return (a % b) < 0 ? q - 1 : q;
+}
+
+STRIP_HD inline int32_t band_weight(int32_t q, int32_t qmax, int32_t ramp)
+{
+    const int32_t v = (q - qmax) + ramp;
+    return v > 0 ? v : 0;
+}
+
+// one band's share of a pixel: the rounded quotient of its weighted differences, N = sum w D, W = sum w >= 1
+STRIP_HD inline int64_t band_term(int64_t N, int64_t W) { return floor_div(2 * N + W, 2 * W); }
+
+// the pixel: NL = sum q S[levels], WL = sum q > 0, b = the sum of the bands' terms
+STRIP_HD inline uint8_t band_pixel(int64_t NL, int64_t WL, int64_t b)
+{
+    const int64_t v = floor_div(NL + (b + 512) * WL, 1024 * WL);
+    return (uint8_t)(v < 0 ? 0 : (v > 255 ? 255 : v));
 }
 
 }  // namespace uwip_sm

@@ -8,9 +8,9 @@ from typing import List, NamedTuple, Optional
 
 import numpy as np
 
-from ._native import UWIP_OK, Context, StripConfig, StripGainConfig, StripSegment, UwipError, batch_of
+from ._native import UWIP_OK, Context, StripBandsConfig, StripConfig, StripGainConfig, StripSegment, UwipError, batch_of
 
-MODES = {"feather": 0, "first": 1, "last": 2}          # UWIP_STRIP_FEATHER / FIRST / LAST
+MODES = {"feather": 0, "first": 1, "last": 2, "multiband": 3}      # UWIP_STRIP_FEATHER / FIRST / LAST / MULTIBAND
 GAIN = 0x100                                           # UWIP_STRIP_GAIN
 
 
@@ -44,6 +44,7 @@ class Strip:
         ctx.call("uwip_strip_create", C.byref(cfg), C.byref(h))
         self._h = h
         self.segments: List[Segment] = []
+        self._injected = False             # the form of the strip: set by its first add
 
     def close(self):
         if getattr(self, "_h", None):
@@ -88,6 +89,7 @@ class Strip:
         self._check(self._l.uwip_strip_add(self._h, C.byref(b), C.c_void_p(H.data_ptr()) if H is not None else None,
                                            C.c_void_p(ratio.data_ptr()) if H is not None else None))
         self.ctx.sync()          # the caller's tensors may go once this returns
+        self._injected = H is not None
         self.segments = []
 
     def layout(self) -> List[Segment]:
@@ -136,11 +138,47 @@ class Strip:
             raise ValueError("gq: [frames, 3]")
         self._check(self._l.uwip_strip_set_gains(self._h, gq.ctypes.data))
 
+    def bands(self, **cfg):
+        """Build the stacks of every frame added so far and keep the ramps for ``render(mode="multiband")``
+        (uwip_strip_bands).  Keywords are ``levels`` (1..4) and ``ramp`` (a sequence of ``levels`` values, each 1..4096) over
+        the defaults 4 and (1, 2, 4, 8).  An ``add`` or a ``reset`` drops the stacks; a new layout keeps them."""
+        c = StripBandsConfig()
+        self._check(self._l.uwip_strip_bands_config_default(C.byref(c)))
+        for k, v in cfg.items():
+            if k == "levels":
+                c.levels = int(v)
+            elif k == "ramp":
+                v = [int(r) for r in v]
+                if len(v) > 4:
+                    raise ValueError("ramp: at most four values")
+                for i, r in enumerate(v):
+                    c.ramp[i] = r
+            else:
+                raise TypeError(f"unknown uwip_strip_bands_config field {k!r}")
+        self._check(self._l.uwip_strip_bands(self._h, C.byref(c)))
+        self.ctx.sync()
+
+    def band_level(self, frame: int, level: int):
+        """After ``bands``: level 1..levels of a frame's stack, uint8 [rows, cols, 3] of the stored geometry (numpy)."""
+        rows, cols = self.stored_size()
+        out = np.zeros((rows, cols, 3), np.uint8)
+        self._check(self._l.uwip_strip_band_level(self._h, int(frame), int(level), out.ctypes.data))
+        return out
+
+    def stored_size(self):
+        """(rows, cols) of the frames as the strip keeps them: as given when H and ratio were injected, the working size
+        (uwip_overlap_working_size) when they were matched."""
+        if self._injected:
+            return int(self.cfg.rows), int(self.cfg.cols)
+        oh, ow = C.c_int(0), C.c_int(0)
+        self.ctx.check(self._l.uwip_overlap_working_size(int(self.cfg.rows), int(self.cfg.cols), C.byref(oh), C.byref(ow)))
+        return oh.value, ow.value
+
     def render(self, segment: int, mode: str = "feather", fill=(0, 0, 0), cover: bool = False, out: "Optional[torch.Tensor]" = None,
                gain: bool = False):
         """One segment of the last ``layout``: a uint8 tensor [rows, cols, 3] (``out``: a tensor of that shape to render
         into, any row stride), and with ``cover`` also the [rows, cols] count of covering frames.  ``gain``: every sample
-        times its frame's gain (``gains`` or ``set_gains`` first)."""
+        times its frame's gain (``gains`` or ``set_gains`` first).  ``mode="multiband"``: ``bands`` first."""
         import torch
 
         if not self.segments:
