@@ -12,11 +12,12 @@ struct StripOut {
     int max_frames = 1024;
     bool gain = false;                            // --strip-gain: gain compensation from the overlaps of consecutive key frames
     int levels = 4;                               // --strip-levels: levels of the stacks of --strip-mode multiband (ramps 1, 2, 4, 8)
+    int seam_prior = 1024;                        // --strip-seam-prior: uwip_strip_seam_config.prior of --strip-mode seam
     unsigned detect_flags = 0, match_flags = 0;
     std::shared_ptr<uw::Strip> strip;             // made at the first key frame; declare a StripOut after its context
 
-    // --strip [--strip-mode feather|first|last|multiband] [--strip-levels N] [--strip-max N] [--strip-gain]; false: an unknown
-    // mode or levels outside 1..4.  --strip-gain without --strip is the caller's to refuse (gain_without_strip)
+    // --strip [--strip-mode feather|first|last|multiband|seam] [--strip-levels N] [--strip-seam-prior N] [--strip-max N]
+    // [--strip-gain]; false: an unknown mode, levels outside 1..4 or a prior outside 0..4096.  --strip-gain without --strip is the caller's to refuse (gain_without_strip)
     bool configure(const Args &a)
     {
         on = a.has("strip");
@@ -26,9 +27,14 @@ struct StripOut {
         else if (m == "first") mode = UWIP_STRIP_FIRST;
         else if (m == "last") mode = UWIP_STRIP_LAST;
         else if (m == "multiband") mode = UWIP_STRIP_MULTIBAND;
+        else if (m == "seam") mode = UWIP_STRIP_SEAM;
         else return false;
         levels = std::atoi(a.get("strip-levels", "4").c_str());
         if (levels < 1 || levels > 4) return false;
+        const std::string p = a.get("strip-seam-prior", "1024");
+        if (p.empty() || p.find_first_not_of("0123456789") != std::string::npos || p.size() > 4) return false;
+        seam_prior = std::atoi(p.c_str());
+        if (seam_prior > 4096) return false;
         max_frames = std::max(1, std::atoi(a.get("strip-max", "1024").c_str()));
         return true;
     }
@@ -49,6 +55,12 @@ struct StripOut {
             uwip_strip_bands_config_default(&bc);
             bc.levels = levels;
             strip->bands(&bc);
+        }
+        if (mode == UWIP_STRIP_SEAM) {                    // after the gains: the costs are those of the gained frames
+            uwip_strip_seam_config sc;
+            uwip_strip_seam_config_default(&sc);
+            sc.prior = seam_prior;
+            strip->seams(&sc);
         }
         for (size_t i = 0; i < segs.size(); ++i) {
             uw::Mat m;

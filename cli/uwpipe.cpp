@@ -11,7 +11,7 @@
 // device (uwip_pipe_keyframe_chain); <prefix>videostrip_report.txt gets its rows with the reference's columns (ID, Frame,
 // Filename, Overlap, Blur), Filename = the enhanced frame that is the key frame.  Overlap in uwpipe_report.txt is then the
 // overlap against the current key frame (nan: not compared).
-// --keyframes --strip [--strip-mode feather|first|last|multiband]: the enhanced key frames are also chained by their homographies and
+// --keyframes --strip [--strip-mode feather|first|last|multiband|seam]: the enhanced key frames are also chained by their homographies and
 // blended into one image per segment, <prefix>strip_NNN.<ext>, with a "Strip:" line per segment after the table of
 // videostrip_report.txt (cli/stripout.hpp).  Refused with --streams, where the frames never reach the host.  --strip-gain: with
 // gain compensation from the overlaps of consecutive key frames (uwip_strip_gains); refused without --strip.
@@ -41,7 +41,7 @@
 
 int main(int argc, char **argv)
 {
-    const Args a = parse_args(argc, argv, {"b", "batch", "c", "w", "window", "k", "p", "lookback", "strip-mode", "strip-max", "strip-levels"});
+    const Args a = parse_args(argc, argv, {"b", "batch", "c", "w", "window", "k", "p", "lookback", "strip-mode", "strip-max", "strip-levels", "strip-seam-prior"});
     if (a.pos.size() < 2 || a.has("h") || a.has("help")) {
         std::printf("uwpipe - bgdehaze -> histretch -> aclahe -> overlap of every frame against its predecessor\n"
                     "usage: uwpipe [-b N] [-c LETTERS] [-w N] [--guard-s] [--min6] [--relative-threshold] [--png] [--device-jpeg]\n"
@@ -59,7 +59,7 @@ int main(int argc, char **argv)
                     "  -p X          minOverlap (default 0.4)\n"
                     "  --lookback D  frames matched ahead per frame (a speed knob; the results do not depend on it)\n"
                     "  --strip       with --keyframes: also blend the enhanced key frames into <prefix>strip_NNN.<ext>, one image per chained\n"
-                    "                segment (--strip-mode feather|first|last|multiband, --strip-levels N for multiband; --strip-max N key frames, default 1024: the strip keeps them\n"
+                    "                segment (--strip-mode feather|first|last|multiband|seam, --strip-levels N for multiband, --strip-seam-prior N for seam; --strip-max N key frames, default 1024: the strip keeps them\n"
                     "                at 640 wide in device memory, about 0.7 MB each, allocated at the first one; key frame N + 1 ends the\n"
                     "                program with an error).  Not with --streams: the frames never reach the host there\n"
                     "  --strip-gain  with --strip: one gain per key frame and colour channel from the overlaps of consecutive key frames\n");
@@ -114,7 +114,7 @@ int main(int argc, char **argv)
         // frame at most a window and a batch back
         uw::Context strip_ctx(ctx);                        // a view: the context stays this program's
         StripOut strip;
-        if (!strip.configure(a)) { std::printf("--strip-mode: feather, first, last or multiband (--strip-levels 1..4)\n"); rc = UWIP_ERR_INVALID; what = "--strip-mode"; goto fail; }
+        if (!strip.configure(a)) { std::printf("--strip-mode: feather, first, last or multiband (--strip-levels 1..4), or seam (--strip-seam-prior 0..4096)\n"); rc = UWIP_ERR_INVALID; what = "--strip-mode"; goto fail; }
         if (strip.gain_without_strip()) { std::printf("--strip-gain is refused without --strip: there is no strip to compensate\n"); rc = UWIP_ERR_INVALID; what = "--strip-gain"; goto fail; }
         strip.detect_flags = cfg.detect_flags; strip.match_flags = cfg.match_flags;
         if (strip.on && !kf) { std::printf("--strip needs --keyframes: the strip is made of the key frames\n"); rc = UWIP_ERR_INVALID; what = "--strip"; goto fail; }

@@ -7,7 +7,7 @@
 // PNG instead) and <prefix>videostrip_report.txt with the reference's TSV columns
 // (main.cpp:263,297,381).  The selector loop is main.cpp:300-394 as written, except that the end
 // of the input ends the program with exit code 0 (the reference calls exit(EXIT_FAILURE), B-14).
-// --strip [--strip-mode feather|first|last|multiband]: the exported key frames are also chained by their homographies and blended
+// --strip [--strip-mode feather|first|last|multiband|seam]: the exported key frames are also chained by their homographies and blended
 // into one image per segment, <prefix>strip_NNN.<ext>, with a "Strip:" line per segment after the report's table
 // (cli/stripout.hpp).  Without the flag the report and the files are what they were.  --strip-gain: the key frames' levels are
 // compensated first, one gain per key frame and channel from the overlaps of consecutive ones (uwip_strip_gains); refused
@@ -38,10 +38,10 @@ struct FrameRec {
 
 int main(int argc, char **argv)
 {
-    const Args a = parse_args(argc, argv, {"k", "windowSize", "s", "timeSkip", "p", "minOverlap", "g", "gpus", "strip-mode", "strip-max", "strip-levels"});
+    const Args a = parse_args(argc, argv, {"k", "windowSize", "s", "timeSkip", "p", "minOverlap", "g", "gpus", "strip-mode", "strip-max", "strip-levels", "strip-seam-prior"});
     if (a.pos.size() < 2 || a.has("h") || a.has("help")) {
         std::printf("videostrip - smart extraction of video frames\n"
-                    "usage: videostrip [-k windowSize] [-s timeSkip] [-p minOverlap] [-r] [--png] [--min6] [--relative-threshold] [-g gpus] [--strip [--strip-mode feather|first|last|multiband] [--strip-levels N] [--strip-gain]] <video.avi (Motion-JPEG) | frame_list.txt> <output_prefix>\n"
+                    "usage: videostrip [-k windowSize] [-s timeSkip] [-p minOverlap] [-r] [--png] [--min6] [--relative-threshold] [-g gpus] [--strip [--strip-mode feather|first|last|multiband|seam] [--strip-levels N] [--strip-gain]] <video.avi (Motion-JPEG) | frame_list.txt> <output_prefix>\n"
                     "  default: any homography found from >= 4 good matches counts, as in the reference (videostrip.cpp:252-272)\n"
                     "  --min6  a homography needs >= 6 RANSAC inliers, else -2.0 (a deviation; --min4 is accepted and names the default)\n"
                     "  default: fixed detector threshold, as SURF's hessianThreshold is fixed (videostrip.cpp:206)\n"
@@ -53,6 +53,9 @@ int main(int argc, char **argv)
                     "          program with an error)\n"
                     "  --strip-mode multiband  blends low frequencies over a wide zone and high frequencies over a narrow one, from a\n"
                     "          stack of --strip-levels N (1..4, default 4) levels per key frame: texture stays sharp where key frames meet\n"
+                    "  --strip-mode seam  cuts every key frame against the one before it along the path where the two differ least, found\n"
+                    "          in the images (after the gains of --strip-gain); --strip-seam-prior N (0..4096, default 1024) is what a pixel\n"
+                    "          of imbalance between the two frames' margins costs, in 1/1024 grey levels\n"
                     "  --strip-gain  with --strip: one gain per key frame and colour channel, solved from the overlaps of consecutive key\n"
                     "          frames, takes the level steps out of the seams\n");
         return 0;
@@ -65,7 +68,7 @@ int main(int argc, char **argv)
     const unsigned match_flags = a.has("min6") ? UWIP_OVERLAP_MIN6 : 0u;
     const unsigned detect_flags = a.has("relative-threshold") ? UWIP_OVERLAP_RELATIVE_THRESHOLD : 0u;
     StripOut strip_cfg;                                    // the options only: the strip itself lives inside its context's scope
-    if (!strip_cfg.configure(a)) { std::printf("--strip-mode: feather, first, last or multiband (--strip-levels 1..4)\n"); return EXIT_FAILURE; }
+    if (!strip_cfg.configure(a)) { std::printf("--strip-mode: feather, first, last or multiband (--strip-levels 1..4), or seam (--strip-seam-prior 0..4096)\n"); return EXIT_FAILURE; }
     if (strip_cfg.gain_without_strip()) { std::printf("--strip-gain is refused without --strip: there is no strip to compensate\n"); return EXIT_FAILURE; }
     strip_cfg.detect_flags = detect_flags; strip_cfg.match_flags = match_flags;
     std::vector<std::string> frames;

@@ -804,8 +804,9 @@ int uwip_pipe_result_params(uwip_pipe *p, uint64_t ticket, int32_t *h_bs, int32_
  * The arithmetic is stated once in csrc/strip_core.hpp and is exact: coordinates in float64 without
  * fused operations, everything behind the source position in integers.
  * A quick look, not a mosaic: working resolution only; exposure compensation as one gain per frame and channel from the
- * overlaps of CONSECUTIVE frames of a segment (uwip_strip_gains, below) and multi-band blending along the feather weights
- * (uwip_strip_bands, below) -- no pairs that are not consecutive, no seam finding, no bundle adjustment, no loop closure.
+ * overlaps of CONSECUTIVE frames of a segment (uwip_strip_gains, below), seams found in those same overlaps
+ * (uwip_strip_seams, below) and multi-band blending along the feather weights, not along the found seams (uwip_strip_bands,
+ * below) -- no pairs that are not consecutive, no bundle adjustment, no loop closure.
  * A strip is bound to the context it was made from (its stream, its thread rule); destroy it before the context. */
 typedef struct uwip_strip uwip_strip;
 typedef struct uwip_strip_config {
@@ -908,6 +909,44 @@ int uwip_strip_band_level(uwip_strip *s, int frame, int level, uint8_t *h_out);
 /* The stack by itself on the host (the source k_strip_stack runs), no device needed: frame [h][w][3] u8 packed, levels 1..4
  * -> out [levels][h][w][3].  A null pointer, w or h outside 1..32768 or levels outside 1..4: UWIP_ERR_INVALID. */
 int uwip_strip_stack_host(const uint8_t *frame, int w, int h, int levels, uint8_t *out);
+/* Seams found in the images (csrc/strip_core.hpp): the other modes decide from geometry alone where one
+ * key frame ends and the next begins, and cut through whatever moved between the two.  Frame k of a segment, other than its
+ * first, has one seam against frame k - 1, in frame k's own pixel grid: the path through the overlap along which the two
+ * frames differ least, one dynamic programme per pair.
+ *   orient   the direction (dx, dy) from frame k - 1's centre to frame k's, in k's coordinates; |dy| >= |dx|: axis 0, the seam is
+ *            a function of x (steps t = x, T = cols; states s = y, S = rows), else axis 1 (t = y, s = x); sign +1 when the
+ *            larger component is >= 0, else -1; orient = axis | (sign < 0 ? 2 : 0);
+ *   cost     C[t][s] = sum_c |Pa[c] - Pb[c]| + prior |a_k - a_p| for a pixel of frame k that frame k - 1 covers (Pb = 1024 x
+ *            the pixel, Pa = the bilinear sample of k - 1, both times their frame's gain when the strip has gains; a = the
+ *            distance along the state axis to the nearer border, a_p of k - 1's nearest pixel), 1 << 22 elsewhere;
+ *   path     E[0] = C[0], E[t][s] = C[t][s] + min(E[t-1][s], E[t-1][s-1], E[t-1][s+1]), ties in that order; the end is the
+ *            smallest s among the minima of E[T-1]; seam[t] in 0..S-1 by walking back, total = the path's cost;
+ *   render   UWIP_STRIP_SEAM: frame k takes a pixel whose nearest source pixel is (t, s) iff sign (s - seam_k[t]) >= 0 (a
+ *            segment's first frame: never); the winner is the largest covering k that takes it, else the smallest covering k;
+ *            out = (P + 512) >> 10 of the winner, as FIRST and LAST.  The cover plane is that of the other modes.
+ * Frames larger than 1023 in either direction (of the stored geometry) are refused: path totals stay below 2^32. */
+typedef struct uwip_strip_seam_config { int32_t prior; int32_t reserved[3]; } uwip_strip_seam_config;   /* prior 0..4096 */
+#define UWIP_STRIP_SEAM 4         /* uwip_strip_render's mode, alone or with UWIP_STRIP_GAIN; uwip_strip_seams first */
+int uwip_strip_seam_config_default(uwip_strip_seam_config *cfg);     /* prior 1024: one grey level per pixel of imbalance */
+/* Find the seams of the frames of the last layout (k_strip_seam_cost, k_strip_seam_path; pairs in rounds of 64), with the
+ * strip's gains if it has any.  cfg NULL = the defaults; a prior outside 0..4096, no layout since the last add, or a stored
+ * frame beyond 1023 x 1023: UWIP_ERR_INVALID, nothing is queued.  The scratch (64 pairs' costs: 4 bytes per pixel) is
+ * allocated here and kept until uwip_strip_reset / uwip_strip_destroy; a failed allocation returns UWIP_ERR_NOMEM and leaves the
+ * strip as it was.  Asynchronous.  An add, a reset, a new layout, uwip_strip_gains and uwip_strip_set_gains drop the seams, and
+ * UWIP_STRIP_SEAM without seams is UWIP_ERR_INVALID. */
+int uwip_strip_seams(uwip_strip *s, const uwip_strip_seam_config *cfg);
+/* Parity tap: h_seam [count][max(cols, rows)] i32 of the stored geometry (entries 0..T-1 of a row are the seam, the others and
+ * a segment's first frame -1), h_orient [count] i32, h_total [count] u64 (a first frame: 0); any may be NULL.  Waits for the
+ * stream. */
+int uwip_strip_seam_values(uwip_strip *s, int32_t *h_seam, int32_t *h_orient, uint64_t *h_total);
+/* Inject seams instead (host, laid out as the tap's), after a layout: the parity hook of the render.  Entries 0..T-1 of a frame
+ * that is not its segment's first must lie in 0..S (S with sign +1: the frame takes nothing) and its orient in 0..3, else
+ * UWIP_ERR_INVALID and the strip's seams stay as they were; a first frame's entries are not read.  Totals read 0 afterwards. */
+int uwip_strip_set_seams(uwip_strip *s, const int32_t *h_seam, const int32_t *h_orient);
+/* The path by itself on the host (the source k_strip_seam_path steps through), no device needed: cost [steps][states], each
+ * entry at most 1 << 22, steps and states 1..1023 -> seam [steps], *total.  Anything else: UWIP_ERR_INVALID, nothing is
+ * written. */
+int uwip_strip_seam_path_host(const uint32_t *cost, int steps, int states, int32_t *seam, uint64_t *total);
 
 #ifdef __cplusplus
 }

@@ -294,9 +294,12 @@ public:
     }
     // the stacks of every frame added so far, for UWIP_STRIP_MULTIBAND (cfg: null = 4 levels, ramps 1, 2, 4, 8); an add drops them
     void bands(const uwip_strip_bands_config *cfg = nullptr) { check(uwip_strip_bands(s_, cfg)); }
+    // after layout() (and gains(), when the costs are to use them): the seam of every frame against the one before it, for
+    // UWIP_STRIP_SEAM (cfg: null = prior 1024); an add, a new layout and new gains drop them
+    void seams(const uwip_strip_seam_config *cfg = nullptr) { check(uwip_strip_seams(s_, cfg)); }
     // level 1..levels of a frame's stack: rows x cols x 3 bytes of the stored geometry (the caller sizes `out`)
     void band_level(int frame, int level, uint8_t *out) { check(uwip_strip_band_level(s_, frame, level, out)); }
-    // one segment of the last layout(); mode = UWIP_STRIP_FEATHER / FIRST / LAST, or MULTIBAND after bands(),
+    // one segment of the last layout(); mode = UWIP_STRIP_FEATHER / FIRST / LAST, MULTIBAND after bands() or SEAM after seams(),
     // | UWIP_STRIP_GAIN after gains() / set_gains()
     void render(int segment, int mode, Mat &out, std::vector<uint8_t> &store)
     {

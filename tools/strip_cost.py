@@ -6,7 +6,9 @@ device-to-device copy of the algorithmic bytes (canvas written plus frames read)
 statistics of the 63 pairs plus the solve, per-kernel device events and wall clock) and the gained render in each mode
 (k_strip_render_gain) next to the ungained one; `bands` (k_strip_stack per level and in all) and the multiband render,
 ungained and gained (k_strip_render_bands, k_strip_render_bands_gain), next to FEATHER of the same run, on both workloads;
-`add` per frame
+`seams` (k_strip_seam_cost next to
+k_strip_gain_stats of the same run, which visits the same pixels with the same sample; k_strip_seam_path per call and per pair)
+and the SEAM render next to LAST of the same run, on both workloads; `add` per frame
 through detect and match (uw_stream frames, wall clock around a drained stream) and `layout` (wall clock).
 Culling: a render visits the frames of its own segment only, so frames of other segments cost nothing by construction (a
 segment's canvas is the box of all its frames: none of them lies outside it).  What culling costs inside a segment is
@@ -54,6 +56,24 @@ def multiband(ctx, s, canvas, reps, feather_ms, copy_ms, gained):
         out["stack_ratio_to_d2d_copy"] = sum(stack) / copy_ms
         out["render"]["ratio_to_d2d_copy"] = ms / copy_ms
     return out
+
+
+def seams(ctx, s, canvas, reps, pairs):
+    """seams with the default prior and the SEAM render of segment 0, next to this run's k_strip_gain_stats and LAST render"""
+    stats = timed(ctx, "k_strip_gain_stats", reps, s.gains)[0]
+    cost, path = timed(ctx, ["k_strip_seam_cost", "k_strip_seam_path"], reps, s.seams)
+    t0 = time.perf_counter()
+    for _ in range(reps):
+        s.seams()
+    wall = (time.perf_counter() - t0) * 1e3 / reps
+    last = timed(ctx, "k_strip_render", reps, lambda: s.render(0, "last", out=canvas))[0]
+    ms = timed(ctx, "k_strip_render_seam", reps, lambda: s.render(0, "seam", out=canvas))[0]
+    msg = timed(ctx, "k_strip_render_seam_gain", reps, lambda: s.render(0, "seam", out=canvas, gain=True))[0]
+    total = s.seam_values()["total"]
+    return {"prior": 1024, "pairs": pairs, "rounds": -(-(pairs + 1) // 64), "gain_stats_ms": stats, "cost_ms": cost, "cost_ratio_to_gain_stats": cost / stats,
+            "path_ms": path, "path_us_per_pair": path * 1e3 / pairs, "ms_wall": wall, "last_ms": last,
+            "render": {"ms": ms, "ratio_to_last": ms / last}, "render_gain": {"ms": msg, "ratio_to_ungained": msg / ms},
+            "mean_total": float(total[1:].astype(np.float64).mean())}
 
 
 def main():
@@ -139,6 +159,7 @@ def main():
         out["render"][mode]["ratio_to_d2d_copy"] = out["render"][mode]["ms"] / copy_ms
     # multi-band blending on the same strip: the stacks of the 64 frames, then the render next to this run's FEATHER
     out["multiband"] = multiband(ctx, s, canvas, reps, out["render"]["feather"]["ms"], copy_ms, gained=True)
+    out["seams"] = seams(ctx, s, canvas, reps, n - 1)          # after the gains of `multiband`'s caller: the costs use them
     s.close()
     del frames, canvas, src, dst
     # culling inside a segment: 1024 frames 15 px apart
@@ -170,6 +191,7 @@ def main():
     mb2 = multiband(ctx, s, canvas2, reps, ms2, 0.0, gained=True)
     mb2["feather_ms"] = ms2
     out["multiband_1024_frames"] = mb2
+    out["seams_1024_frames"] = seams(ctx, s, canvas2, reps, n2 - 1)
     s.close()
     del f2, canvas2, cover2
     # add through resize, detect and match: 16 frames per call, the stream drained around the timed calls

@@ -126,6 +126,12 @@ class StripBandsConfig(C.Structure):
     _fields_ = [("levels", C.c_int32), ("ramp", C.c_int32 * 4), ("reserved", C.c_int32 * 3)]
 
 
+class StripSeamConfig(C.Structure):
+    """Mirror of ``uwip_strip_seam_config`` (16 bytes)."""
+
+    _fields_ = [("prior", C.c_int32), ("reserved", C.c_int32 * 3)]
+
+
 # uwip_keyframe_chain_host's callbacks
 KF_OVERLAP_FN = C.CFUNCTYPE(C.c_float, C.c_void_p, C.c_int32, C.c_int32)
 KF_BLUR_FN = C.CFUNCTYPE(C.c_float, C.c_void_p, C.c_int32)
@@ -269,6 +275,11 @@ SIGNATURES = {
     "uwip_strip_bands": (C.c_int, [_P, C.POINTER(StripBandsConfig)]),
     "uwip_strip_band_level": (C.c_int, [_P, C.c_int, C.c_int, _P]),
     "uwip_strip_stack_host": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P]),
+    "uwip_strip_seam_config_default": (C.c_int, [C.POINTER(StripSeamConfig)]),
+    "uwip_strip_seams": (C.c_int, [_P, C.POINTER(StripSeamConfig)]),
+    "uwip_strip_seam_values": (C.c_int, [_P, _P, _P, _P]),
+    "uwip_strip_set_seams": (C.c_int, [_P, _P, _P]),
+    "uwip_strip_seam_path_host": (C.c_int, [_P, C.c_int, C.c_int, _P, _P]),
 }
 
 

@@ -10,7 +10,12 @@
 //                    LDS and adds them to stats[k] with one 64-bit atomic per quantity;
 //   k_strip_gain_solve  one lane runs strip_core.hpp's gain_solve() over the statistics;
 //   k_strip_stack    multi-band blending, the frames' stacks: one level of every frame per launch, the tile and its halo in LDS;
-//   k_strip_render_bands  the gather of k_strip_render, one pixel per thread, blending the stacks' bands (UWIP_STRIP_MULTIBAND).
+//   k_strip_render_bands  the gather of k_strip_render, one pixel per thread, blending the stacks' bands (UWIP_STRIP_MULTIBAND);
+//   k_strip_seam_cost  seams, the measurement: the tile of k_strip_gain_stats, one cost per pixel of frame k against frame k - 1,
+//                    written in the order the path reads it (transposed through LDS when the path runs along x);
+//   k_strip_seam_path  one workgroup per pair runs strip_core.hpp's seam_step() over the steps, the states in parallel, E double-
+//                    buffered in LDS, back pointers of 2 bits in LDS or in global scratch; one lane walks back.
+//   k_strip_render<UWIP_STRIP_SEAM> paints every frame over the ones below it on its side of its seam.
 // Everything inside the anonymous namespace is also compiled by the host compiler and run on host threads by
 // tests/strip_emulated.cpp (no HIP-only intrinsics in there).
 #include "uwip_internal.hpp"
@@ -38,6 +43,37 @@ struct StripRender {
     uint8_t fill[4];
     int32_t vec;                          // bytes per store of the write-out: 16, 4 or 1
     const int32_t *gq = nullptr;          // [frames][3] gains in 1/4096 for k_strip_render<MODE, true>; null = none
+};
+
+// what k_strip_render<UWIP_STRIP_SEAM> takes besides: the seams stay in global memory (a wave's 64 pixels read neighbouring entries)
+struct StripSeams {
+    const int32_t *seam = nullptr;        // [frames][L]: each frame's seam against the one before
+    const int32_t *orient = nullptr;      // [frames]: axis | sign of each seam
+    int32_t L = 0;
+};
+
+constexpr int kSeamRound = 64;                               // pairs whose costs the scratch holds at a time
+constexpr int kSeamStates = (uwip_sm::kSeamMaxSide + kRenderThreads - 1) / kRenderThreads;    // most states a thread of the path owns
+constexpr int kSeamBackLdsWords = 15360;                     // back pointers kept in LDS: 60 KB (360 x 640 / 16 words are 57.6 KB)
+constexpr int kSeamCostPad = kTileW + 4;                     // the transposed read's 16 rows x 4 columns: 64 different banks
+
+struct StripSeam {
+    const uint8_t *store;                 // [frames][h][w][3]
+    size_t fstride;
+    int32_t w, h;
+    const double *G, *Ginv;               // [frames][9]
+    const int32_t *seg;                   // [frames]
+    const int32_t *gq;                    // [frames][3] or null
+    uwip_sm::SeamParams P;
+    int32_t k0;                           // the round's first frame: blockIdx.y (cost) / blockIdx.x (path) = frame - k0 = the slot
+    int32_t tiles_x;
+    uint32_t *cost;                       // [round][T][S]
+    uint32_t *back;                       // [round][back_stride] words of back pointers for k_strip_seam_path<false>
+    size_t back_stride;
+    int32_t *orient;                      // [frames]
+    int32_t *seam;                        // [frames][L]
+    int32_t L;                            // max(w, h)
+    unsigned long long *total;            // [frames]
 };
 
 struct StripGainStats {
@@ -112,13 +148,115 @@ __global__ __launch_bounds__(64) void k_strip_gain_solve(uwip_sm::GainParams P, 
     uwip_sm::gain_solve(P, reinterpret_cast<const uint64_t *>(stats), seg, n, gq, g, scr);
 }
 
-// GAIN: every sample is multiplied by its frame's gain (a.gq) before it is blended; false is the kernel without gains
+// Frame k = k0 + blockIdx.y against frame k - 1: the cost of every pixel of the tile, into cost[slot] in path order [t][s].
+// Axis 1 (t = y, s = x): a wave's 64 pixels of a row are 64 consecutive entries.  Axis 0 (t = x, s = y): the tile goes through
+// LDS and comes out as 64 runs of 16 consecutive entries.
+__global__ __launch_bounds__(kRenderThreads) void k_strip_seam_cost(StripSeam a)
+{
+    __shared__ uint32_t s_c[kTileH][kSeamCostPad];
+    __shared__ int32_t s_orient;
+    const int32_t k = a.k0 + (int32_t)blockIdx.y;
+    if (k == 0 || a.seg[k] != a.seg[k - 1]) return;        // the first frame of a segment has no seam (uniform: no barrier yet)
+    const int32_t tid = (int32_t)threadIdx.x;
+    const int32_t tx0 = ((int32_t)blockIdx.x % a.tiles_x) * kTileW, ty0 = ((int32_t)blockIdx.x / a.tiles_x) * kTileH;
+    const int32_t lx = tid & (kTileW - 1), ly = tid / kTileW, x = tx0 + lx;
+    if (tid == 0) {
+        s_orient = uwip_sm::seam_orient(a.G + 9 * (size_t)(k - 1), a.Ginv + 9 * (size_t)k, a.w, a.h);
+        if (blockIdx.x == 0) a.orient[k] = s_orient;
+    }
+    __syncthreads();
+    const int32_t axis = uwip_sm::seam_axis(s_orient);
+    const uint8_t *fk = a.store + (size_t)k * a.fstride, *fp = a.store + (size_t)(k - 1) * a.fstride;
+    const int32_t *gk = a.gq ? a.gq + 3 * (size_t)k : nullptr, *gp = a.gq ? a.gq + 3 * (size_t)(k - 1) : nullptr;
+    uint32_t *C = a.cost + (size_t)blockIdx.y * ((size_t)a.w * a.h);
+    double G[9], Ap[9];
+#pragma unroll
+    for (int i = 0; i < 9; ++i) { G[i] = a.G[9 * (size_t)k + i]; Ap[i] = a.Ginv[9 * (size_t)(k - 1) + i]; }
+#pragma unroll
+    for (int j = 0; j < kPix; ++j) {
+        const int32_t r = ly + j * (kRenderThreads / kTileW), y = ty0 + r;
+        const bool in = x < a.w && y < a.h;
+        const uint32_t c = in ? uwip_sm::seam_cost(a.P, fk, fp, G, Ap, gk, gp, axis, x, y, a.w, a.h) : 0u;
+        if (axis) { if (in) C[(size_t)y * a.w + x] = c; }
+        else s_c[r][lx] = c;
+    }
+    if (axis) return;                                      // uniform
+    __syncthreads();
+    for (int32_t i = tid; i < kTileW * kTileH; i += kRenderThreads) {
+        const int32_t cx = i / kTileH, cy = i % kTileH;
+        if (tx0 + cx < a.w && ty0 + cy < a.h) C[(size_t)(tx0 + cx) * a.h + (ty0 + cy)] = s_c[cy][cx];
+    }
+}
+
+// The pair of frame k = k0 + blockIdx.x: T sequential steps, a thread owns the states tid, tid + 256, ...  The back pointer of
+// (t, s) is bits 2 (t & 15) of word [t >> 4][s]: a thread collects 16 steps of a state in a register, so no two threads share
+// a word.  LDS_BACK: the words are in LDS (the launch code has checked that they fit), otherwise in a.back.
+template <bool LDS_BACK>
+__global__ __launch_bounds__(kRenderThreads) void k_strip_seam_path(StripSeam a)
+{
+    __shared__ uint32_t s_E[2][uwip_sm::kSeamMaxSide + 1];
+    __shared__ uint32_t s_back[LDS_BACK ? kSeamBackLdsWords : 1];
+    const int32_t k = a.k0 + (int32_t)blockIdx.x, tid = (int32_t)threadIdx.x;
+    int32_t *seam = a.seam + (size_t)k * a.L;
+    if (k == 0 || a.seg[k] != a.seg[k - 1]) {              // a segment's first frame: no seam (uniform)
+        for (int32_t i = tid; i < a.L; i += kRenderThreads) seam[i] = -1;
+        if (tid == 0) { a.orient[k] = 0; a.total[k] = 0; }
+        return;
+    }
+    const int32_t axis = uwip_sm::seam_axis(a.orient[k]);
+    const int32_t T = axis ? a.h : a.w, S = axis ? a.w : a.h;
+    const uint32_t *C = a.cost + (size_t)blockIdx.x * ((size_t)a.w * a.h);
+    uint32_t *back = LDS_BACK ? s_back : a.back + (size_t)blockIdx.x * a.back_stride;
+    uint32_t acc[kSeamStates], next[kSeamStates];
+#pragma unroll
+    for (int j = 0; j < kSeamStates; ++j) {
+        const int32_t s = tid + j * kRenderThreads;
+        acc[j] = 0; next[j] = 0;
+        if (s < S) {
+            s_E[0][s] = C[s];
+            if (T > 1) next[j] = C[(size_t)S + s];
+        }
+    }
+    __syncthreads();
+    for (int32_t t = 1; t < T; ++t) {
+        const uint32_t *prev = s_E[(t - 1) & 1];
+        uint32_t *cur = s_E[t & 1];
+        const bool flush = (t & 15) == 15 || t == T - 1;
+#pragma unroll
+        for (int j = 0; j < kSeamStates; ++j) {
+            const int32_t s = tid + j * kRenderThreads;
+            if (s >= S) continue;
+            const uint32_t c = next[j];
+            if (t + 1 < T) next[j] = C[(size_t)(t + 1) * S + s];       // the next step's cost is on its way during this one
+            uint32_t bp;
+            cur[s] = uwip_sm::seam_step(prev, S, s, c, bp);
+            acc[j] |= bp << (2 * (t & 15));
+            if (flush) { back[(size_t)(t >> 4) * S + s] = acc[j]; acc[j] = 0; }
+        }
+        __syncthreads();                                   // E[t] is complete; E[t - 1] may be overwritten by step t + 1
+    }
+    for (int32_t i = T + tid; i < a.L; i += kRenderThreads) seam[i] = -1;
+    if (tid != 0) return;
+    const uint32_t *last = s_E[(T - 1) & 1];
+    int32_t s = 0;
+    for (int32_t i = 1; i < S; ++i) if (last[i] < last[s]) s = i;
+    a.total[k] = last[s];
+    for (int32_t t = T - 1; t >= 0; --t) {
+        seam[t] = s;
+        if (t > 0) s = uwip_sm::seam_back(s, (back[(size_t)(t >> 4) * S + s] >> (2 * (t & 15))) & 3u);
+    }
+}
+
+// GAIN: every sample is multiplied by its frame's gain (a.gq) before it is blended; false is the kernel without gains.
+// UWIP_STRIP_SEAM keeps two candidates per pixel -- the largest covering frame on its own side of its seam (den, num) and the
+// smallest covering frame (lo, nlo) -- so the result does not depend on the order of the tile's listing.
 template <int MODE, bool GAIN = false>
-__global__ __launch_bounds__(kRenderThreads) void k_strip_render(StripRender a)
+__global__ __launch_bounds__(kRenderThreads) void k_strip_render(StripRender a, StripSeams q = StripSeams())
 {
     __shared__ double s_A[kCullChunk][9];
     __shared__ int32_t s_idx[kCullChunk];
     __shared__ int32_t s_gq[GAIN ? kCullChunk : 1][3];
+    __shared__ int32_t s_or[MODE == UWIP_STRIP_SEAM ? kCullChunk : 1];       // the listed frames' orient; -1: the segment's first
     __shared__ uint32_t s_n;
     __shared__ uint32_t s_tile[kTileH * kTileRowBytes / 4];
     const int32_t tid = (int32_t)threadIdx.x;
@@ -131,8 +269,13 @@ __global__ __launch_bounds__(kRenderThreads) void k_strip_render(StripRender a)
     // FEATHER: num / den; FIRST / LAST: the winner's index in den and its P in num
     int64_t num[kPix][3], den[kPix];
     uint32_t cnt[kPix];
+    int32_t lo[kPix], nlo[kPix][3];                       // UWIP_STRIP_SEAM alone
 #pragma unroll
     for (int j = 0; j < kPix; ++j) { num[j][0] = num[j][1] = num[j][2] = 0; den[j] = MODE == UWIP_STRIP_FEATHER ? 0 : -1; cnt[j] = 0; }
+    if (MODE == UWIP_STRIP_SEAM) {
+#pragma unroll
+        for (int j = 0; j < kPix; ++j) { lo[j] = -1; nlo[j][0] = nlo[j][1] = nlo[j][2] = 0; }
+    }
 
     for (int32_t base = 0; base < a.count; base += kCullChunk) {
         __syncthreads();                                   // the previous chunk's list has been read by everyone
@@ -146,6 +289,7 @@ __global__ __launch_bounds__(kRenderThreads) void k_strip_render(StripRender a)
                 s_idx[slot] = g;
                 for (int i = 0; i < 9; ++i) s_A[slot][i] = a.Ginv[9 * (size_t)g + i];
                 if (GAIN) for (int c = 0; c < 3; ++c) s_gq[slot][c] = a.gq[3 * (size_t)g + c];
+                if (MODE == UWIP_STRIP_SEAM) s_or[slot] = g == a.first ? -1 : q.orient[g];
             }
         }
         __syncthreads();
@@ -166,6 +310,24 @@ __global__ __launch_bounds__(kRenderThreads) void k_strip_render(StripRender a)
                 uwip_sm::Tap t;
                 if (!uwip_sm::sample(A, px, (double)(Y + a.y0), a.w, a.h, t)) continue;
                 cnt[j] += 1u;
+                if (MODE == UWIP_STRIP_SEAM) {
+                    const int32_t o = s_or[e];
+                    const bool best = o >= 0 && g > den[j] &&
+                                      uwip_sm::seam_side(o, q.seam + (size_t)g * q.L, t.x + (t.fx >= 16), t.y + (t.fy >= 16));
+                    const bool lowest = lo[j] < 0 || g < lo[j];
+                    if (!best && !lowest) continue;
+                    const uint8_t *r0 = f + ((size_t)t.y * a.w) * 3, *r1 = f + ((size_t)t.y1 * a.w) * 3;
+#pragma unroll
+                    for (int c = 0; c < 3; ++c) {
+                        int32_t P = uwip_sm::bilinear(t, r0[t.x * 3 + c], r0[t.x1 * 3 + c], r1[t.x * 3 + c], r1[t.x1 * 3 + c]);
+                        if (GAIN) P = uwip_sm::apply_gain(P, gq[c]);
+                        if (best) num[j][c] = P;
+                        if (lowest) nlo[j][c] = P;
+                    }
+                    if (best) den[j] = g;
+                    if (lowest) lo[j] = g;
+                    continue;
+                }
                 if (MODE != UWIP_STRIP_FEATHER) {
                     const bool wins = den[j] < 0 || (MODE == UWIP_STRIP_LAST ? g > den[j] : g < den[j]);
                     if (!wins) continue;
@@ -197,6 +359,8 @@ __global__ __launch_bounds__(kRenderThreads) void k_strip_render(StripRender a)
                 if (den[j] > 0) v = (uint8_t)((num[j][c] + 512 * den[j]) / (1024 * den[j]));
             } else if (den[j] >= 0) {
                 v = (uint8_t)((num[j][c] + 512) >> 10);
+            } else if (MODE == UWIP_STRIP_SEAM && lo[j] >= 0) {
+                v = (uint8_t)((nlo[j][c] + 512) >> 10);
             }
             tile[r * kTileRowBytes + lx * 3 + c] = v;
         }
@@ -479,6 +643,12 @@ struct uwip_strip {
     size_t bands_bytes = 0;
     int band_count = 0;                    // frames the stacks were built for
     uwip_sm::BandParams band{};            // levels 0: no stacks (an add, a reset: dropped; a new layout keeps them)
+    uint8_t *seam_block = nullptr;         // seam [max_frames][max(w, h)], orient [max_frames], total [max_frames]: allocated by
+    int32_t *seam = nullptr, *orient = nullptr;    // uwip_strip_seams / uwip_strip_set_seams, freed by reset and destroy
+    unsigned long long *total = nullptr;
+    uint8_t *seam_scratch = nullptr;       // the costs of a round of pairs, and their back pointers where LDS cannot hold them
+    size_t seam_scratch_bytes = 0;
+    bool seamed = false;                   // seams found or set since the last layout and the last gains (dropped as the gains are)
 
     int fail(int code, const char *what) { err = what; return code; }
     int from_ctx(int rc) { if (rc) err = ctx->err; return rc; }
@@ -545,6 +715,8 @@ UWIP_API int uwip_strip_destroy(uwip_strip *s)
     if (s->feats) uwip_features_destroy(s->feats);
     if (s->store) uwip_free(s->ctx, s->store);
     if (s->bands) uwip_free(s->ctx, s->bands);
+    if (s->seam_block) uwip_free(s->ctx, s->seam_block);
+    if (s->seam_scratch) uwip_free(s->ctx, s->seam_scratch);
     if (s->block) uwip_free(s->ctx, s->block);
     delete s;
     return UWIP_OK;
@@ -555,11 +727,15 @@ UWIP_API int uwip_strip_reset(uwip_strip *s)
     if (!s) return UWIP_ERR_INVALID;
     s->form = 0; s->count = 0; s->last_n = 0; s->have_prev = false; s->laid = -1; s->cursor = 0; s->gained = false;
     s->h_segs.clear();
-    s->band.levels = 0;
-    if (s->bands) {                                        // the stacks' store goes with the frames: a strip that asks again pays again
+    s->band.levels = 0; s->seamed = false;
+    if (s->bands || s->seam_block || s->seam_scratch) {    // these stores go with the frames: a strip that asks again pays again
         if (uwip_enter(s->ctx) == UWIP_OK) (void)uwip_stream_wait(s->ctx);
-        uwip_free(s->ctx, s->bands);
+        if (s->bands) uwip_free(s->ctx, s->bands);
+        if (s->seam_block) uwip_free(s->ctx, s->seam_block);
+        if (s->seam_scratch) uwip_free(s->ctx, s->seam_scratch);
         s->bands = nullptr; s->bands_bytes = 0;
+        s->seam_block = nullptr; s->seam = s->orient = nullptr; s->total = nullptr;
+        s->seam_scratch = nullptr; s->seam_scratch_bytes = 0;
     }
     return UWIP_OK;
 }
@@ -637,7 +813,7 @@ UWIP_API int uwip_strip_add(uwip_strip *s, const uwip_batch_u8 *frames, const do
         UWIP_HIP(ctx, hipMemcpyAsync(s->H + 9 * (size_t)s->count, d_H_inject, 72 * (size_t)n, hipMemcpyDeviceToDevice, ctx->stream));
         UWIP_HIP(ctx, hipMemcpyAsync(s->ratio + s->count, d_ratio_inject, 4 * (size_t)n, hipMemcpyDeviceToDevice, ctx->stream));
     }
-    s->form = form; s->have_prev = true; s->last_n = n; s->count += n; s->gained = false; s->band.levels = 0;
+    s->form = form; s->have_prev = true; s->last_n = n; s->count += n; s->gained = false; s->seamed = false; s->band.levels = 0;
     return UWIP_OK;
 }
 
@@ -654,7 +830,7 @@ static int strip_lay_out(uwip_strip *s)
     uwip_ctx *ctx = s->ctx;
     if (s->laid == s->count) return UWIP_OK;
     s->h_segs.clear();
-    s->gained = false;
+    s->gained = false; s->seamed = false;
     if (s->count > 0) {
         uwip_sm::ChainOut o;
         o.G = s->G; o.Ginv = s->Ginv; o.seg = s->seg; o.box = s->box; o.segs = s->segs; o.nseg = s->nseg;
@@ -714,8 +890,10 @@ UWIP_API int uwip_strip_render(uwip_strip *s, int segment, int mode, const uint8
     if (segment < 0 || segment >= (int)s->h_segs.size()) return s->fail(UWIP_ERR_INVALID, "uwip_strip_render: no such segment");
     const bool gain = (mode & UWIP_STRIP_GAIN) != 0;
     mode &= ~UWIP_STRIP_GAIN;
-    if (mode != UWIP_STRIP_FEATHER && mode != UWIP_STRIP_FIRST && mode != UWIP_STRIP_LAST && mode != UWIP_STRIP_MULTIBAND)
+    if (mode != UWIP_STRIP_FEATHER && mode != UWIP_STRIP_FIRST && mode != UWIP_STRIP_LAST && mode != UWIP_STRIP_MULTIBAND && mode != UWIP_STRIP_SEAM)
         return s->fail(UWIP_ERR_INVALID, "uwip_strip_render: unknown mode");
+    if (mode == UWIP_STRIP_SEAM && !s->seamed)
+        return s->fail(UWIP_ERR_INVALID, "uwip_strip_render: UWIP_STRIP_SEAM without uwip_strip_seams or uwip_strip_set_seams since the last layout and gains");
     if (mode == UWIP_STRIP_MULTIBAND && (s->band.levels == 0 || s->band_count != s->count))
         return s->fail(UWIP_ERR_INVALID, "uwip_strip_render: UWIP_STRIP_MULTIBAND without uwip_strip_bands since the last add");
     if (gain && !s->gained) return s->fail(UWIP_ERR_INVALID, "uwip_strip_render: UWIP_STRIP_GAIN without uwip_strip_gains or uwip_strip_set_gains since the last layout");
@@ -749,6 +927,16 @@ UWIP_API int uwip_strip_render(uwip_strip *s, int segment, int mode, const uint8
         return UWIP_OK;
     }
     const dim3 grid(uwip_cdiv((size_t)g.cols, kTileW), uwip_cdiv((size_t)g.rows, kTileH));
+    if (mode == UWIP_STRIP_SEAM) {
+        StripSeams q;
+        q.seam = s->seam; q.orient = s->orient; q.L = std::max(s->w, s->h);
+        if (gain) a.gq = s->gq;
+        uwip_kscope ks(ctx, gain ? "k_strip_render_seam_gain" : "k_strip_render_seam");
+        if (gain) k_strip_render<UWIP_STRIP_SEAM, true><<<grid, kRenderThreads, 0, ctx->stream>>>(a, q);
+        else k_strip_render<UWIP_STRIP_SEAM><<<grid, kRenderThreads, 0, ctx->stream>>>(a, q);
+        UWIP_HIP(ctx, hipGetLastError());
+        return UWIP_OK;
+    }
     if (gain) {
         a.gq = s->gq;
         uwip_kscope ks(ctx, "k_strip_render_gain");
@@ -896,7 +1084,7 @@ UWIP_API int uwip_strip_gains(uwip_strip *s, const uwip_strip_gain_config *cfg)
         k_strip_gain_solve<<<1, 64, 0, ctx->stream>>>(P, s->stats, s->seg, s->count, s->gq, s->g, s->fb);     // fb: free once the chain has run
         if (hipError_t e = hipGetLastError()) return s->from_ctx(ctx->fail(UWIP_ERR_HIP, "k_strip_gain_solve", hipGetErrorString(e)));
     }
-    s->gained = true;
+    s->gained = true; s->seamed = false;
     return UWIP_OK;
 }
 
@@ -930,7 +1118,7 @@ UWIP_API int uwip_strip_set_gains(uwip_strip *s, const int32_t *h_gq)
     if (!rc) rc = uwip_memcpy_h2d(s->ctx, s->g, g.data(), 24 * N);
     if (rc) return s->from_ctx(rc);
     if (hipError_t e = hipMemsetAsync(s->stats, 0, 8 * uwip_sm::kGainStats * N, s->ctx->stream)) return s->from_ctx(s->ctx->fail(UWIP_ERR_HIP, "hipMemsetAsync", hipGetErrorString(e)));
-    s->gained = true;
+    s->gained = true; s->seamed = false;
     return UWIP_OK;
 }
 
@@ -944,6 +1132,131 @@ UWIP_API int uwip_strip_gain_solve_host(const uint64_t *h_stats, const int32_t *
     uwip_sm::gain_solve(gain_params(cfg), h_stats, h_seg, n, gq.data(), g.data(), scr.data());
     if (h_gq) std::copy(gq.begin(), gq.end(), h_gq);
     if (h_g) std::copy(g.begin(), g.end(), h_g);
+    return UWIP_OK;
+}
+
+// ---- seams ----------------------------------------------------------------------------------------------------------------
+UWIP_API int uwip_strip_seam_config_default(uwip_strip_seam_config *cfg)
+{
+    if (!cfg) return UWIP_ERR_INVALID;
+    std::memset(cfg, 0, sizeof *cfg);
+    cfg->prior = 1024;
+    return UWIP_OK;
+}
+
+// seam, orient and total of every frame the strip can hold, one allocation
+static int seam_arrays(uwip_strip *s)
+{
+    if (s->seam_block) return UWIP_OK;
+    const size_t N = (size_t)s->cfg.max_frames, L = (size_t)std::max(s->w, s->h);
+    const size_t o_total = 0, o_seam = align256(8 * N), o_orient = o_seam + align256(4 * L * N);
+    void *d = nullptr;
+    if (int rc = uwip_malloc(s->ctx, o_orient + align256(4 * N), &d)) return rc;
+    s->seam_block = (uint8_t *)d;
+    s->total = (unsigned long long *)(s->seam_block + o_total); s->seam = (int32_t *)(s->seam_block + o_seam); s->orient = (int32_t *)(s->seam_block + o_orient);
+    return UWIP_OK;
+}
+
+UWIP_API int uwip_strip_seams(uwip_strip *s, const uwip_strip_seam_config *cfg)
+{
+    if (!s) return UWIP_ERR_INVALID;
+    uwip_ctx *ctx = s->ctx;
+    if (int rc_e = uwip_enter(ctx)) return s->from_ctx(rc_e);
+    if (cfg && (cfg->prior < 0 || cfg->prior > 4096)) return s->fail(UWIP_ERR_INVALID, "uwip_strip_seams: prior 0..4096");
+    if (s->laid != s->count || s->count == 0) return s->fail(UWIP_ERR_INVALID, "uwip_strip_seams: call uwip_strip_layout first");
+    if (std::max(s->w, s->h) > uwip_sm::kSeamMaxSide) return s->fail(UWIP_ERR_INVALID, "uwip_strip_seams: stored frames of at most 1023 x 1023");
+    const size_t wh = (size_t)s->w * s->h;
+    const size_t back_words = std::max((size_t)uwip_cdiv((size_t)s->w, 16) * s->h, (size_t)uwip_cdiv((size_t)s->h, 16) * s->w);   // either axis
+    const bool lds_back = back_words <= (size_t)kSeamBackLdsWords;
+    const size_t round = (size_t)std::min(kSeamRound, s->cfg.max_frames);
+    const size_t o_back = align256(4 * wh * round), need = o_back + (lds_back ? 0 : align256(4 * back_words * round));
+    if (need > s->seam_scratch_bytes) {
+        void *d = nullptr;                                   // the new block first: a failure leaves the strip as it was
+        if (int rc = uwip_malloc(ctx, need, &d)) return s->from_ctx(rc);
+        if (s->seam_scratch) {
+            if (hipError_t e = uwip_stream_wait(ctx)) { uwip_free(ctx, d); return s->from_ctx(ctx->fail(UWIP_ERR_HIP, "uwip_stream_wait", hipGetErrorString(e))); }
+            uwip_free(ctx, s->seam_scratch);
+        }
+        s->seam_scratch = (uint8_t *)d; s->seam_scratch_bytes = need;
+    }
+    if (int rc = seam_arrays(s)) return s->from_ctx(rc);
+    StripSeam a;
+    a.store = s->store; a.fstride = wh * 3; a.w = s->w; a.h = s->h;
+    a.G = s->G; a.Ginv = s->Ginv; a.seg = s->seg; a.gq = s->gained ? s->gq : nullptr;
+    a.P.prior = cfg ? cfg->prior : 1024;
+    a.tiles_x = (int32_t)uwip_cdiv((size_t)s->w, kTileW);
+    a.cost = (uint32_t *)s->seam_scratch; a.back = lds_back ? nullptr : (uint32_t *)(s->seam_scratch + o_back); a.back_stride = back_words;
+    a.orient = s->orient; a.seam = s->seam; a.L = std::max(s->w, s->h); a.total = s->total;
+    s->seamed = false;
+    for (int k0 = 0; k0 < s->count; k0 += (int)round) {    // a round's costs are read by its paths before the next round's are written: one stream
+        const unsigned nr = (unsigned)std::min((int)round, s->count - k0);
+        a.k0 = k0;
+        {
+            uwip_kscope ks(ctx, "k_strip_seam_cost");
+            k_strip_seam_cost<<<dim3((unsigned)a.tiles_x * uwip_cdiv((size_t)s->h, kTileH), nr), kRenderThreads, 0, ctx->stream>>>(a);
+            if (hipError_t e = hipGetLastError()) return s->from_ctx(ctx->fail(UWIP_ERR_HIP, "k_strip_seam_cost", hipGetErrorString(e)));
+        }
+        uwip_kscope ks(ctx, "k_strip_seam_path");
+        if (lds_back) k_strip_seam_path<true><<<nr, kRenderThreads, 0, ctx->stream>>>(a);
+        else k_strip_seam_path<false><<<nr, kRenderThreads, 0, ctx->stream>>>(a);
+        if (hipError_t e = hipGetLastError()) return s->from_ctx(ctx->fail(UWIP_ERR_HIP, "k_strip_seam_path", hipGetErrorString(e)));
+    }
+    s->seamed = true;
+    return UWIP_OK;
+}
+
+UWIP_API int uwip_strip_seam_values(uwip_strip *s, int32_t *h_seam, int32_t *h_orient, uint64_t *h_total)
+{
+    if (!s) return UWIP_ERR_INVALID;
+    if (int rc_e = uwip_enter(s->ctx)) return s->from_ctx(rc_e);
+    if (s->laid != s->count || !s->seamed) return s->fail(UWIP_ERR_INVALID, "uwip_strip_seam_values: no seams since the last layout and gains");
+    const size_t N = (size_t)s->count, L = (size_t)std::max(s->w, s->h);
+    int rc = UWIP_OK;
+    if (!rc && h_seam) rc = uwip_memcpy_d2h(s->ctx, h_seam, s->seam, 4 * L * N);
+    if (!rc && h_orient) rc = uwip_memcpy_d2h(s->ctx, h_orient, s->orient, 4 * N);
+    if (!rc && h_total) rc = uwip_memcpy_d2h(s->ctx, h_total, s->total, 8 * N);
+    if (!rc && !h_seam && !h_orient && !h_total) rc = uwip_sync(s->ctx);
+    return s->from_ctx(rc);
+}
+
+UWIP_API int uwip_strip_set_seams(uwip_strip *s, const int32_t *h_seam, const int32_t *h_orient)
+{
+    if (!s) return UWIP_ERR_INVALID;
+    if (int rc_e = uwip_enter(s->ctx)) return s->from_ctx(rc_e);
+    if (!h_seam || !h_orient) return s->fail(UWIP_ERR_INVALID, "uwip_strip_set_seams: h_seam and h_orient");
+    if (s->laid != s->count || s->count == 0) return s->fail(UWIP_ERR_INVALID, "uwip_strip_set_seams: call uwip_strip_layout first");
+    const size_t N = (size_t)s->count, L = (size_t)std::max(s->w, s->h);
+    std::vector<int32_t> seam(L * N, -1), orient(N, 0);
+    std::vector<uint64_t> total(N, 0);
+    for (const uwip_strip_segment &g : s->h_segs)
+        for (int k = g.first + 1; k < g.first + g.count; ++k) {          // a segment's first frame has no seam: its entries are not read
+            const int32_t o = h_orient[k];
+            if (o < 0 || o > 3) return s->fail(UWIP_ERR_INVALID, "uwip_strip_set_seams: an orient outside 0..3");
+            const int32_t T = uwip_sm::seam_axis(o) ? s->h : s->w, S = uwip_sm::seam_axis(o) ? s->w : s->h;
+            for (int32_t t = 0; t < T; ++t) {
+                const int32_t v = h_seam[L * (size_t)k + t];
+                if (v < 0 || v > S) return s->fail(UWIP_ERR_INVALID, "uwip_strip_set_seams: a seam entry outside 0..states");
+                seam[L * (size_t)k + t] = v;
+            }
+            orient[k] = o;
+        }
+    if (int rc = seam_arrays(s)) return s->from_ctx(rc);
+    int rc = uwip_memcpy_h2d(s->ctx, s->seam, seam.data(), 4 * L * N);
+    if (!rc) rc = uwip_memcpy_h2d(s->ctx, s->orient, orient.data(), 4 * N);
+    if (!rc) rc = uwip_memcpy_h2d(s->ctx, s->total, total.data(), 8 * N);
+    if (rc) return s->from_ctx(rc);
+    s->seamed = true;
+    return UWIP_OK;
+}
+
+UWIP_API int uwip_strip_seam_path_host(const uint32_t *cost, int steps, int states, int32_t *seam, uint64_t *total)
+{
+    if (!cost || !seam || !total || steps < 1 || states < 1 || steps > uwip_sm::kSeamMaxSide || states > uwip_sm::kSeamMaxSide) return UWIP_ERR_INVALID;
+    const size_t n = (size_t)steps * states;
+    for (size_t i = 0; i < n; ++i) if (cost[i] > uwip_sm::kSeamOutside) return UWIP_ERR_INVALID;
+    std::vector<uint32_t> E(2 * (size_t)states);
+    std::vector<uint8_t> back(n);
+    *total = uwip_sm::seam_path(cost, steps, states, seam, E.data(), back.data());
     return UWIP_OK;
 }
 

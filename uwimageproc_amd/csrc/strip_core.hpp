@@ -1,7 +1,8 @@
 // The arithmetic of the strip mosaic, stated ONCE for the device (strip.hip: k_strip_chain, k_strip_render, k_strip_gain_stats,
-// k_strip_gain_solve, k_strip_stack, k_strip_render_bands), the host (uwip_strip_chain_host, uwip_strip_gain_solve_host,
-// uwip_strip_stack_host) and the emulation harnesses (tests/strip_emulated.cpp, tests/strip_gain_emulated.cpp,
-// tests/strip_band_emulated.cpp).  tests/_strip_mirror.py, tests/_strip_gain_mirror.py and tests/_strip_band_mirror.py restate it
+// k_strip_gain_solve, k_strip_stack, k_strip_render_bands, k_strip_seam_cost, k_strip_seam_path), the host (uwip_strip_chain_host,
+// uwip_strip_gain_solve_host, uwip_strip_stack_host, uwip_strip_seam_path_host) and the emulation harnesses
+// (tests/strip_emulated.cpp, tests/strip_gain_emulated.cpp, tests/strip_band_emulated.cpp, tests/strip_seam_emulated.cpp).
+// tests/_strip_mirror.py, tests/_strip_gain_mirror.py, tests/_strip_band_mirror.py and tests/_strip_seam_mirror.py restate it
 // in numpy and take nothing from here; the tests compare the two bit for bit, which is why
 //   - every coordinate is float64, products and sums are separate operations (the library and the harness are built with
 //     -ffp-contract=off), sums are written ((a*x) + (b*y)) + c, and divisions are IEEE divisions;
@@ -344,6 +345,104 @@ STRIP_HD inline uint8_t band_pixel(int64_t NL, int64_t WL, int64_t b)
 {
     const int64_t v = floor_div(NL + (b + 512) * WL, 1024 * WL);
     return (uint8_t)(v < 0 ? 0 : (v > 255 ? 255 : v));
+}
+
+// ---- seams found in the overlaps of consecutive frames ----------------------------------------------------------------------
+// Frame k of a segment (not its first) has one seam against frame k - 1, in frame k's own pixel grid: the path through the
+// overlap along which the two (gained) frames differ least, one dynamic programme per pair.  seam_orient() picks the axis the
+// path runs along, seam_cost() is one entry of the pair's cost, seam_step() one state of one step of the programme, seam_path()
+// the whole of it, seam_side() the render's question.  Costs are exact integers below 2^22 (kSeamOutside where the pair has no
+// sample), so with at most 1023 steps every path total stays below 2^32.
+struct SeamParams { int32_t prior; };     // 0 .. 4096: cost, in 1/1024 grey levels, per pixel of imbalance between the two frames' margins
+constexpr uint32_t kSeamOutside = 1u << 22;
+constexpr int32_t kSeamMaxSide = 1023;    // the largest stored frame side a seam is computed for
+
+// orient = axis | (sign < 0 ? 2 : 0).  axis 0: the seam is a function of x (steps t = x, states s = y); axis 1: of y.
+STRIP_HD inline int32_t seam_axis(int32_t orient) { return orient & 1; }
+STRIP_HD inline int32_t seam_sign(int32_t orient) { return (orient & 2) ? -1 : 1; }
+
+// Gp = G of frame k - 1, A = Ginv of frame k: the direction from k - 1's centre to k's centre, in k's coordinates
+STRIP_HD inline int32_t seam_orient(const double *Gp, const double *A, int32_t w, int32_t h)
+{
+    const double cx = (double)(w - 1) * 0.5, cy = (double)(h - 1) * 0.5;
+    double dx = 0.0, dy = 0.0, px, py;
+    if (gain_point(Gp, cx, cy, px, py)) {
+        const double d = ((A[6] * px) + (A[7] * py)) + A[8];
+        if (d > 0.0) {
+            const double u = (((A[0] * px) + (A[1] * py)) + A[2]) / d;
+            const double v = (((A[3] * px) + (A[4] * py)) + A[5]) / d;
+            if (finite_d(u) && finite_d(v)) { dx = cx - u; dy = cy - v; }
+        }
+    }
+    if (fabs(dy) >= fabs(dx)) return dy >= 0.0 ? 0 : 2;
+    return dx >= 0.0 ? 1 : 3;
+}
+
+// C of pixel (x, y) of frame k: fk / fp are frames k and k - 1 (w x h BGR, packed), G of frame k, Ap = Ginv of frame k - 1,
+// gk / gp their gains in 1/4096 (null: 4096)
+STRIP_HD inline uint32_t seam_cost(const SeamParams &P, const uint8_t *fk, const uint8_t *fp, const double *G, const double *Ap,
+                                   const int32_t *gk, const int32_t *gp, int32_t axis, int32_t x, int32_t y, int32_t w, int32_t h)
+{
+    double px, py;
+    Tap t;
+    if (!gain_point(G, (double)x, (double)y, px, py)) return kSeamOutside;
+    if (!sample(Ap, px, py, w, h, t)) return kSeamOutside;
+    const uint8_t *b = fk + ((size_t)y * w + x) * 3;
+    const uint8_t *r0 = fp + ((size_t)t.y * w) * 3, *r1 = fp + ((size_t)t.y1 * w) * 3;
+    int32_t D = 0;
+    for (int c = 0; c < 3; ++c) {
+        const int32_t Pb = apply_gain(1024 * (int32_t)b[c], gk ? gk[c] : 4096);
+        const int32_t Pa = apply_gain(bilinear(t, r0[t.x * 3 + c], r0[t.x1 * 3 + c], r1[t.x * 3 + c], r1[t.x1 * 3 + c]), gp ? gp[c] : 4096);
+        D += Pa > Pb ? Pa - Pb : Pb - Pa;
+    }
+    const int32_t xn = t.x + (t.fx >= 16), yn = t.y + (t.fy >= 16);
+    const int32_t S = axis ? w : h, s = axis ? x : y, sp = axis ? xn : yn;
+    const int32_t ak = s < S - 1 - s ? s : S - 1 - s, ap = sp < S - 1 - sp ? sp : S - 1 - sp;
+    return (uint32_t)(D + P.prior * (ak > ap ? ak - ap : ap - ak));
+}
+
+// One state of one step: E[t][s] from E[t - 1] (`prev`, S states) and c = C[t][s]; bp = 0, 1, 2 for the predecessor s, s - 1,
+// s + 1 (ties in that order)
+STRIP_HD inline uint32_t seam_step(const uint32_t *prev, int32_t S, int32_t s, uint32_t c, uint32_t &bp)
+{
+    uint32_t m = prev[s];
+    bp = 0;
+    if (s > 0 && prev[s - 1] < m) { m = prev[s - 1]; bp = 1; }
+    if (s + 1 < S && prev[s + 1] < m) { m = prev[s + 1]; bp = 2; }
+    return c + m;
+}
+
+STRIP_HD inline int32_t seam_back(int32_t s, uint32_t bp) { return bp == 1 ? s - 1 : (bp == 2 ? s + 1 : s); }
+
+// The path: cost [T][S] -> seam [T], the total.  E [2][S] and back [T][S] (2 bits used of each byte) are scratch.
+STRIP_HD inline uint64_t seam_path(const uint32_t *cost, int32_t T, int32_t S, int32_t *seam, uint32_t *E, uint8_t *back)
+{
+    for (int32_t s = 0; s < S; ++s) E[s] = cost[s];
+    for (int32_t t = 1; t < T; ++t) {
+        const uint32_t *prev = E + (size_t)((t - 1) & 1) * S;
+        uint32_t *cur = E + (size_t)(t & 1) * S;
+        for (int32_t s = 0; s < S; ++s) {
+            uint32_t bp;
+            cur[s] = seam_step(prev, S, s, cost[(size_t)t * S + s], bp);
+            back[(size_t)t * S + s] = (uint8_t)bp;
+        }
+    }
+    const uint32_t *last = E + (size_t)((T - 1) & 1) * S;
+    int32_t s = 0;
+    for (int32_t i = 1; i < S; ++i) if (last[i] < last[s]) s = i;
+    const uint64_t total = last[s];
+    for (int32_t t = T - 1; t >= 0; --t) {
+        seam[t] = s;
+        if (t > 0) s = seam_back(s, back[(size_t)t * S + s]);
+    }
+    return total;
+}
+
+// does frame k take the pixel whose nearest source pixel is (xn, yn)?  seam = frame k's row of seams
+STRIP_HD inline bool seam_side(int32_t orient, const int32_t *seam, int32_t xn, int32_t yn)
+{
+    const int32_t t = seam_axis(orient) ? yn : xn, s = seam_axis(orient) ? xn : yn;
+    return seam_sign(orient) * (s - seam[t]) >= 0;
 }
 
 }  // namespace uwip_sm

@@ -8,9 +8,9 @@ from typing import List, NamedTuple, Optional
 
 import numpy as np
 
-from ._native import UWIP_OK, Context, StripBandsConfig, StripConfig, StripGainConfig, StripSegment, UwipError, batch_of
+from ._native import UWIP_OK, Context, StripBandsConfig, StripConfig, StripGainConfig, StripSeamConfig, StripSegment, UwipError, batch_of
 
-MODES = {"feather": 0, "first": 1, "last": 2, "multiband": 3}      # UWIP_STRIP_FEATHER / FIRST / LAST / MULTIBAND
+MODES = {"feather": 0, "first": 1, "last": 2, "multiband": 3, "seam": 4}      # UWIP_STRIP_FEATHER / FIRST / LAST / MULTIBAND / SEAM
 GAIN = 0x100                                           # UWIP_STRIP_GAIN
 
 
@@ -165,6 +165,36 @@ class Strip:
         self._check(self._l.uwip_strip_band_level(self._h, int(frame), int(level), out.ctypes.data))
         return out
 
+    def seams(self, **cfg):
+        """After ``layout`` (and after ``gains``, whose gains the costs then use): find the seam of every frame against the
+        frame before it, for ``render(mode="seam")`` (uwip_strip_seams).  Keyword: ``prior`` (0..4096) over the default 1024.
+        An ``add``, a ``reset``, a new layout, ``gains`` and ``set_gains`` drop the seams."""
+        c = StripSeamConfig()
+        self._check(self._l.uwip_strip_seam_config_default(C.byref(c)))
+        for k, v in cfg.items():
+            if k != "prior":
+                raise TypeError(f"unknown uwip_strip_seam_config field {k!r}")
+            c.prior = int(v)
+        self._check(self._l.uwip_strip_seams(self._h, C.byref(c)))
+        self.ctx.sync()
+
+    def seam_values(self):
+        """After ``seams`` or ``set_seams``: dict of seam [n, max(cols, rows)] int32 of the stored geometry (-1 beyond a
+        seam's steps and for a segment's first frame), orient [n] int32 (axis | 2 for sign -1), total [n] uint64 (numpy)."""
+        n, (rows, cols) = len(self), self.stored_size()
+        seam, ori, total = np.zeros((n, max(rows, cols)), np.int32), np.zeros(n, np.int32), np.zeros(n, np.uint64)
+        self._check(self._l.uwip_strip_seam_values(self._h, seam.ctypes.data, ori.ctypes.data, total.ctypes.data))
+        return {"seam": seam, "orient": ori, "total": total}
+
+    def set_seams(self, seam, orient):
+        """After ``layout``: inject seams [n, max(cols, rows)] (entries 0..states) and orients [n] (0..3) instead of finding
+        them."""
+        rows, cols = self.stored_size()
+        seam, orient = np.ascontiguousarray(seam, np.int32), np.ascontiguousarray(orient, np.int32)
+        if seam.shape != (len(self), max(rows, cols)) or orient.shape != (len(self),):
+            raise ValueError("seam: [frames, max(cols, rows)], orient: [frames]")
+        self._check(self._l.uwip_strip_set_seams(self._h, seam.ctypes.data, orient.ctypes.data))
+
     def stored_size(self):
         """(rows, cols) of the frames as the strip keeps them: as given when H and ratio were injected, the working size
         (uwip_overlap_working_size) when they were matched."""
@@ -178,7 +208,8 @@ class Strip:
                gain: bool = False):
         """One segment of the last ``layout``: a uint8 tensor [rows, cols, 3] (``out``: a tensor of that shape to render
         into, any row stride), and with ``cover`` also the [rows, cols] count of covering frames.  ``gain``: every sample
-        times its frame's gain (``gains`` or ``set_gains`` first).  ``mode="multiband"``: ``bands`` first."""
+        times its frame's gain (``gains`` or ``set_gains`` first).  ``mode="multiband"``: ``bands`` first; ``mode="seam"``:
+        ``seams`` or ``set_seams`` first."""
         import torch
 
         if not self.segments:
